@@ -4,6 +4,21 @@
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU)
 
+A plain run does what the headline figure needs: it sets up, runs the W
+warmup steps and the clock ramp, times the K steps, writes their outputs if
+--dump-outputs DIR is given, and prints the line (`value`, `ms_per_step` =
+the timed region / K).  --full adds every other measurement and check named
+below (cpu_baseline, parity, other_inputs / generated_inputs, config_d,
+p50 / p90, kernel_ms, the rooflines), each in passes of its own after the
+timed region; without it those fields are null or absent.
+--dump-outputs DIR: the arrays the timed steps returned, DIR/<name>.npy in
+float64 (episode workloads: the log record of each timed step as step_index,
+step_cost, step_state (x, y, phi, v, beta), step_status (step, p, episode,
+found, status), and the last step's winner record as winner_index / _cost /
+_found / _control / _trajectory).  The candidate batches are seeded and the
+episode is restarted one replay before the timed one, so the same arguments
+give the same files in every run.
+
 Workloads:
   C (default)  N=10 horizon, 1e6 candidates per GPU, moving-target episode
                (reference operator schedule); by default each step's candidate
@@ -179,11 +194,22 @@ def parse():
                     help="override the workload's per-GPU candidate count")
     ap.add_argument("--dump-log", default=None,
                     help="write the device episode's per-step log (rank 0) to this JSON file")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the "
+                         "cpu_baseline, the parity legs against the CPU oracle, the other input "
+                         "modes, the config-D sub-results, the latency passes and the per-kernel "
+                         "and roofline figures.  Without it the run sets up, warms up, times "
+                         "the K steps and prints the line (those fields null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed as DIR/<name>.npy "
+                         "(float64; rank 0): see dump_outputs()")
     ap.add_argument("--traffic-json", default=None,
                     help="PMC-derived HBM bytes per launch for the roofline 'traffic' field "
                          "(tools/pmc.sh + tools/pmc_summary.py on the same kernel and config; "
                          "default: the committed round-2 summary of the roofline's kernel)")
     args = ap.parse_args()
+    if args.dump_outputs and args.host_loop:
+        ap.error("--dump-outputs: the device-resident episode only (not --host-loop)")
     if args.integrator is None and args.workload in ("A", "R"):
         args.integrator = "qk21"          # the drop-in's default: the reference's arithmetic
     if args.integrator is None:
@@ -332,8 +358,11 @@ def bench_dropin(args, wl, eng, rank, world, cpu):
         mmt.predictive_control = orig
         mmt.reset_state()
     n_calls = len(rets)
+    if args.dump_outputs and rank == 0:
+        # the last timed scenario run: what each predictive_control call returned
+        dump_outputs(args.dump_outputs, {"returns": [list(r) for r in rets[-len(calls):]]})
     same = worst = 0
-    for i, r in enumerate(rets):
+    for i, r in enumerate(rets if args.full else []):
         want = calls[i % len(calls)]["ret"]
         same += r[3:] == want[3:]
         worst = max(worst, max(abs(a - b) for a, b in zip(r[:3], want[:3])))
@@ -350,8 +379,9 @@ def bench_dropin(args, wl, eng, rank, world, cpu):
         "p50_ms": percentile(ms, 50), "p90_ms": percentile(ms, 90),
         "p50_note": "host time per predictive_control call, end to end (the reference's "
                     "0.361 s p50 is the same call on one CPU core, SURVEY §6)",
+        "full": args.full,
         "parity": {"calls": n_calls, "chosen_control_identical": same,
-                   "max_abs_pose_diff": worst},
+                   "max_abs_pose_diff": worst} if args.full else None,
         "roofline": None, "cpu_baseline": cpu,
     }
     if rank == 0:
@@ -451,7 +481,7 @@ def main():
                                      os.environ.get("MASTER_PORT")]}), flush=True)
         return
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = (cpu_baseline_fulltree(args.cpu_seconds) if args.workload in ("F", "G")
                else cpu_baseline_dropin(args.cpu_seconds) if args.workload in ("A", "R")
                else cpu_baseline(wl, args.cpu_seconds))
@@ -493,11 +523,11 @@ def main():
 
     out, ep, pool = bench_episode(args, wl, eng, rank, world, device, cpu)
     chain = getattr(ep, "chain", False) and args.inputs == "resident" and not args.host_loop
-    if chain and args.parity_steps > 0:
+    if args.full and chain and args.parity_steps > 0:
         # checker, after every timed region: logged steps re-scanned on the
         # host by the oracle in the reference's own arithmetic (qk21)
         out["parity"] = parity_pass(args, eng, ep, pool, rank, world, device)
-    if args.workload == "C" and chain and not args.no_config_d:
+    if args.full and args.workload == "C" and chain and not args.no_config_d:
         # BASELINE config D (N=12, 1.25e6 candidates per GPU = 1e7 at 8) in
         # the same run: at --gpus N the form the driver's scaling run measures
         ep_form = getattr(ep, "p2p", False)
@@ -509,6 +539,7 @@ def main():
         d_args = argparse.Namespace(**vars(args))
         d_args.candidates_per_gpu = None
         d_args.dump_log = None               # --dump-log is the main episode's
+        d_args.dump_outputs = None           # ... and so is --dump-outputs
         d_out, ep, pool = bench_episode(d_args, WORKLOADS["D"], eng, rank, world, device, None,
                                         sub=True)
         out["config_d"] = {k: d_out[k] for k in (
@@ -528,6 +559,7 @@ def main():
         t_args = argparse.Namespace(**vars(args))
         t_args.candidates_per_gpu = -(-D_TOTAL // world)
         t_args.dump_log = None
+        t_args.dump_outputs = None
         t_out, ep, pool = bench_episode(t_args, WORKLOADS["D"], eng, rank, world, device, None,
                                         sub=True)
         out["config_d_total"] = {k: t_out[k] for k in (
@@ -552,6 +584,50 @@ def _plain(o):
     if isinstance(o, np.generic):
         return o.item()
     raise TypeError(f"not JSON serializable: {type(o).__name__}")
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each of the timed path's output arrays as
+    DIR/<name>.npy (float64).  The inputs are seeded and the episode is
+    restarted a fixed number of steps before the timed region ends
+    (run_steps), so two runs with the same arguments write the same files."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def episode_outputs(snap, k, n_steps):
+    """What the K timed steps of a device episode returned to their caller,
+    from the copies run_steps took right after the timed region: per timed
+    step the log record (chosen candidate, its cost, the state moved to, the
+    episode's bookkeeping), and the last step's winner record (mpc_result_t:
+    the chosen control and its per-step states) where the step form leaves
+    the global winner in one buffer."""
+    import numpy as np
+    from diplomjourney_amd.abi import LOG_BYTES, result_from_bytes
+    rec = np.dtype([("step", "<i8"), ("index", "<i8"), ("p", "<i4"), ("episode", "<i4"),
+                    ("found", "<i4"), ("status", "<i4"), ("cost", "<f8"), ("x", "<f8"),
+                    ("y", "<f8"), ("phi", "<f8"), ("v", "<f8"), ("beta", "<f8")])
+    assert rec.itemsize == LOG_BYTES
+    log = np.frombuffer(snap["log"], dtype=rec)
+    end = snap["steps_enqueued"]
+    first = max(0, end - min(k, len(log)))
+    log = log[(log["episode"] >= 1) & (log["step"] >= first) & (log["step"] < end)]
+    log = log[np.argsort(log["step"], kind="stable")]
+    assert len(log) == end - first, (len(log), first, end)
+    out = {"step_index": log["index"], "step_cost": log["cost"],
+           "step_state": np.stack([log[f] for f in ("x", "y", "phi", "v", "beta")], axis=1),
+           "step_status": np.stack([log[f] for f in ("step", "p", "episode", "found", "status")],
+                                   axis=1)}
+    if snap["winner"] is not None:
+        w = result_from_bytes(snap["winner"])
+        out["winner_index"] = [w.index]
+        out["winner_cost"] = [w.cost]
+        out["winner_found"] = [w.found]
+        out["winner_control"] = [w.v, w.beta]
+        out["winner_trajectory"] = [[w.traj[s][c] for c in range(3)] for s in range(n_steps)]
+    return out
 
 
 def bench_episode(args, wl, eng, rank, world, device, cpu, sub=False):
@@ -606,11 +682,15 @@ def bench_episode(args, wl, eng, rank, world, device, cpu, sub=False):
     kernel = ("k_episode_run" if run_form else "k_episode_chain" if chained
               else (P2P_KERNEL if p2p else XCHG_KERNEL) if xchg_chain
               else "k_rollout_argmin_stream")
-    main_run = run_steps(args, ep, pool, use_graph, world, device, run_form=run_form)
+    main_run = run_steps(args, ep, pool, use_graph, world, device, run_form=run_form,
+                         dump=bool(args.dump_outputs))
     use_graph = main_run["graph"]
     kern_ms = main_run["kernel_in_step_ms"]
     sustained_ms = None
-    if run_form and use_graph:
+    full = args.full
+    if not full:
+        pass   # the timed K steps only: no pass for the per-kernel figures (kern_ms is None)
+    elif run_form and use_graph:
         # the run's device time per step inside the timed replay; sustained:
         # a 200-step run replayed (reported beside it)
         kern_ms = main_run["kernel_timed_ms"]
@@ -635,12 +715,12 @@ def bench_episode(args, wl, eng, rank, world, device, cpu, sub=False):
     elif hasattr(ep, "partials"):
         kern_ms = kernel_pass(ep, pool if pool is not None else
                               make_pool(eng, ep, n_steps, 4))
-    if chained and not sub:
+    if full and chained and not sub:
         # for comparison: the same controls through the rollout kernel alone
         # (the chained launch adds block 0's completion of the previous step)
         rollout_ms = kernel_pass(ep, soa_pool(ep, pool))
     other = generated = None
-    if not args.host_loop and not args.no_second_pass and not sub:
+    if full and not args.host_loop and not args.no_second_pass and not sub:
         # the other input mode, same episode machinery, for comparison
         other_pool = None if inputs == "resident" else make_pool(eng, ep, n_steps, args.steps)
         # (gloo collectives stage through the host: not capturable)
@@ -664,12 +744,12 @@ def bench_episode(args, wl, eng, rank, world, device, cpu, sub=False):
                              note="over the whole step (generated rollout + selection): a "
                                   "lower bound of the rollout kernel's rate")}
     host_ms = None
-    if not args.host_loop and not exchange and not sub:
+    if full and not args.host_loop and not exchange and not sub:
         host_ms = host_latency_pass(ep, pool)
     elapsed = main_run["elapsed"]
     chain_step = getattr(ep, "chain", False) and inputs == "resident"
     bytes_launch = 16.0 * n_steps * ep.n_local
-    achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
+    achieved = bytes_launch / (kern_ms * 1e-3) / 1e9 if kern_ms else None
     value = n_total * args.steps / elapsed
     # self-validation: a chained / exchange step whose bounded device wait
     # timed out ran on speculated constants or dropped a rank's candidate —
@@ -699,9 +779,11 @@ def bench_episode(args, wl, eng, rank, world, device, cpu, sub=False):
         episodes = log[-1].episode
     else:
         episodes = ep.episodes
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, episode_outputs(main_run["snapshot"], args.steps, n_steps))
     out = {
         "metric": METRIC, "value": value, "unit": "rollouts/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup,
+        "steps": args.steps, "warmup": args.warmup, "full": full,
         "ramp": {"steps": main_run["ramp_steps"], "seconds": main_run["ramp_s"],
                  "note": "untimed replays of the K steps after the W warmup steps and before "
                          "the timed region (>= 300 steps and >= --ramp-seconds): the GPU's "
@@ -763,7 +845,7 @@ def bench_episode(args, wl, eng, rank, world, device, cpu, sub=False):
                            if (chained or (xchg_chain and p2p)) and use_graph
                            else "events around back-to-back launches (graph_timed / per launch)"),
         "kernel_ms_sustained": sustained_ms,
-        "roofline": (None if inputs == "generated" else
+        "roofline": (None if inputs == "generated" or achieved is None else
                      roofline(achieved, bytes_launch, args.traffic_json, kernel=kernel,
                               layout="tiled" if tiled else "soa")),
         "roofline_rollout_only": (None if rollout_ms is None else
@@ -775,6 +857,8 @@ def bench_episode(args, wl, eng, rank, world, device, cpu, sub=False):
         "generated_inputs": generated,
         "cpu_baseline": cpu,
     }
+    if not full:
+        out["kernel_ms_note"] = None
     if out["roofline"] is not None and pool is not None:
         # the same kernel against the measured read ceiling of
         # its own access pattern and its VALU issue share (PMC counters of the
@@ -1117,8 +1201,14 @@ LAYOUT_DOC = {
 }
 
 
-def run_steps(args, ep, pool, use_graph, world, device, run_form=False):
-    """Warmup, the timed K steps, then the eager latency passes.
+def run_steps(args, ep, pool, use_graph, world, device, run_form=False, dump=False):
+    """Warmup, the timed K steps, then (--full) the eager latency passes.
+
+    A device episode is restarted (reset) after the clock ramp, exactly one
+    untimed replay before the timed one: the ramp's length depends on the
+    clock, and so the timed steps are steps K .. 2K-1 of the episode in every
+    run.  dump: keep copies of the log and of the winner record as the timed
+    region left them (`snapshot`, for --dump-outputs).
 
     With a graph (the default): the K steps — and a chained episode's closing
     flush — are captured once into ONE graph (one replay call: the least host
@@ -1213,6 +1303,8 @@ def run_steps(args, ep, pool, use_graph, world, device, run_form=False):
     # the GPU late (kernel trace: 28-31.5 us kernels starting 34-38 us apart).
     # Same box, 4 interleaved pairs at K = 20: 33.0-33.6 vs 33.5-34.3 us per
     # step (profiles/r05/driver_ab.txt)
+    if hasattr(ep, "state"):
+        ep.reset()       # (with P2P mailboxes a collective: every rank is here)
     run_k()
     ran += args.steps
     torch.cuda.synchronize()
@@ -1241,6 +1333,18 @@ def run_steps(args, ep, pool, use_graph, world, device, run_form=False):
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    snapshot = None
+    if dump:
+        # what the timed steps left: the log, and the buffer that holds the
+        # global winner of the last step (none in the two-launch exchange form)
+        win = ep.local if not ep.exchange else ep.winner if ep.chain else None
+        snapshot = {"steps_enqueued": ep.steps_enqueued,
+                    "log": ep.log.cpu().numpy().tobytes(),
+                    "winner": None if win is None else win.cpu().numpy().tobytes()}
+    if not getattr(args, "full", False):
+        return {"elapsed": elapsed, "graph": graph is not None, "ramp_steps": ran,
+                "ramp_s": ramp_s, "snapshot": snapshot, "kernel_timed_ms": None, "flush_ms": 0.0,
+                "p50_ms": None, "p90_ms": None, "kernel_in_step_ms": None}
     # latency pass: one event per step start (more events per step would add
     # their own host cost to an eagerly launched step)
     marks = [Ev() for _ in range(args.steps + 1)]
@@ -1267,7 +1371,7 @@ def run_steps(args, ep, pool, use_graph, world, device, run_form=False):
     torch.cuda.synchronize()
     flush_ms = (sum(a.elapsed_time(b) for a, b in fl) / n_kern) if has_flush else 0.0
     return {"elapsed": elapsed, "graph": graph is not None, "ramp_steps": ran,
-            "ramp_s": ramp_s,
+            "ramp_s": ramp_s, "snapshot": snapshot,
             "kernel_timed_ms": max(timed_ms - flush_ms, 0.0) / args.steps,
             "flush_ms": flush_ms,
             "p50_ms": percentile(step_gpu_ms, 50),
@@ -1575,11 +1679,17 @@ def bench_robots(args, wl, eng, rank, world, cpu):
         elapsed = float(t.item())
     res = results_from_device(out)
     assert all(r.index >= 0 for r in res)
+    if args.dump_outputs and rank == 0:
+        # the last step's winner per robot of this rank (mpc_result_t each)
+        dump_outputs(args.dump_outputs, {
+            "index": [r.index for r in res], "cost": [r.cost for r in res],
+            "control": [[r.v, r.beta] for r in res],
+            "trajectory": [r.trajectory() for r in res]})
     kern_ms = sum(kern) / len(kern)
     bytes_launch = 16.0 * n_steps * R * cand
     outd = {
         "metric": METRIC, "value": R_total * cand * args.steps / elapsed, "unit": "rollouts/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": wl["desc"], "n_steps": n_steps, "robots_per_gpu": R,
@@ -1597,6 +1707,31 @@ def bench_robots(args, wl, eng, rank, world, cpu):
         print(json.dumps(outd), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def fulltree_launch_ms(args, rmm, world, reps=20):
+    """ms per mpc_fulltree_argmin call on the episode's current problem (see
+    bench_fulltree)."""
+    import math as _m
+    import torch
+    import torch.distributed as dist
+    from diplomjourney_amd.abi import MpcFulltreeProblem
+    from diplomjourney_amd.expansion import fulltree_argmin
+    feng, (fvg, fbg) = rmm._device()
+    fp = MpcFulltreeProblem(float(rmm.x), float(rmm.y), float(rmm.phi), float(rmm.x_t),
+                            float(rmm.y_t), float(rmm.x_0), float(rmm.y_0),
+                            float(_m.atan(rmm.x_t / rmm.y_t)), float(rmm.L), float(rmm.t),
+                            float(rmm.t + rmm.delta_t))
+    shard = (dist.get_rank(), world) if world > 1 else (0, 1)
+    for _ in range(3):
+        fulltree_argmin(feng, fp, fvg, fbg, float("inf"), args.integrator, *shard)
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    ev[0].record()
+    for _ in range(reps):
+        fulltree_argmin(feng, fp, fvg, fbg, float("inf"), args.integrator, *shard)
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]) / reps
 
 
 def bench_fulltree(args, wl, eng, rank, world, cpu):
@@ -1652,28 +1787,16 @@ def bench_fulltree(args, wl, eng, rank, world, cpu):
     # on the episode's last problem, back to back between HIP events on the
     # current stream: the duration the rooflines divide by (the step above
     # adds the drop-in's host work and the 200-B read-back).
-    from diplomjourney_amd.abi import MpcFulltreeProblem
-    from diplomjourney_amd.expansion import fulltree_argmin
-    feng, (fvg, fbg) = rmm._device()
-    fp = MpcFulltreeProblem(float(rmm.x), float(rmm.y), float(rmm.phi), float(rmm.x_t),
-                            float(rmm.y_t), float(rmm.x_0), float(rmm.y_0),
-                            float(_m.atan(rmm.x_t / rmm.y_t)), float(rmm.L), float(rmm.t),
-                            float(rmm.t + rmm.delta_t))
-    shard = (dist.get_rank(), world) if world > 1 else (0, 1)
-    for _ in range(3):
-        fulltree_argmin(feng, fp, fvg, fbg, float("inf"), args.integrator, *shard)
-    reps = 20
-    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    ev[0].record()
-    for _ in range(reps):
-        fulltree_argmin(feng, fp, fvg, fbg, float("inf"), args.integrator, *shard)
-    ev[1].record()
-    torch.cuda.synchronize()
-    launch_ms = ev[0].elapsed_time(ev[1]) / reps
-    flops = FT_FLOPS_PER_LEAF[args.integrator] * leaves / world / (launch_ms * 1e-3)   # per GPU
+    launch_ms = fulltree_launch_ms(args, rmm, world) if args.full else None
+    if args.dump_outputs and rank == 0:
+        # per timed step: the pose and control moved to, and the criterion
+        dump_outputs(args.dump_outputs, {"trace": trace[-args.steps:]})
+    # per GPU
+    flops = (FT_FLOPS_PER_LEAF[args.integrator] * leaves / world / (launch_ms * 1e-3)
+             if launch_ms else None)
     out = {
         "metric": METRIC, "value": leaves * args.steps / elapsed, "unit": "leaves/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": per_step * 1e3, "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": wl["desc"], "s1": s1, "leaves_per_step": leaves,
@@ -1684,13 +1807,14 @@ def bench_fulltree(args, wl, eng, rank, world, cpu):
         "launch_ms": launch_ms,
         "launch_note": "mpc_fulltree_argmin's three launches (k_ft_leaves ~96%), HIP events "
                        "around 20 back-to-back calls on the last step's problem",
-        "roofline": {"bound": "valu-fp64", "achieved": flops / 1e12,
-                     "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": flops / 1e12 / FP64_VECTOR_PEAK_TFLOPS, "traffic": None,
-                     "kernel": "k_ft_leaves",
-                     "note": "algorithmic fp64 ops per leaf as written (FT_FLOPS_PER_LEAF) over "
-                             "launch_ms; leaves are generated from the index, no HBM stream"},
-        "roofline_valu": valu_roofline("k_ft_leaves", args.integrator, launch_ms * world,
+        "roofline": None if flops is None else {
+            "bound": "valu-fp64", "achieved": flops / 1e12,
+            "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": flops / 1e12 / FP64_VECTOR_PEAK_TFLOPS, "traffic": None,
+            "kernel": "k_ft_leaves",
+            "note": "algorithmic fp64 ops per leaf as written (FT_FLOPS_PER_LEAF) over "
+                    "launch_ms; leaves are generated from the index, no HBM stream"},
+        "roofline_valu": valu_roofline("k_ft_leaves", args.integrator, (launch_ms or 0) * world,
                                        leaves, 3,
                                        note="counted fp64 ops of one MPC step (all leaves, PMC) "
                                             "over launch_ms x ranks"),
@@ -1736,6 +1860,9 @@ def bench_tree_episodes(args, wl, eng, rank, world, cpu):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     calls, stop, cands = eps.read_progress()
+    if args.dump_outputs and rank == 0:
+        # per episode of this rank: MPC calls made, stop bits, candidates scored
+        dump_outputs(args.dump_outputs, {"calls": calls, "stop": stop, "candidates": cands})
     t = torch.tensor([elapsed, float(calls.sum()), float(cands.sum()), float(calls.max())],
                      dtype=torch.float64, device=eng.device)
     if world > 1:
@@ -1751,7 +1878,7 @@ def bench_tree_episodes(args, wl, eng, rank, world, cpu):
         stops[k] = stops.get(k, 0) + 1
     out = {
         "metric": METRIC, "value": n_cands / elapsed, "unit": "rollouts/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup,
+        "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": elapsed / max(1, lockstep) * 1e3,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
         "data": "synthetic (the script's seeded start/target draws)",
@@ -1815,6 +1942,9 @@ def bench_episodes(args, wl, eng, rank, world, cpu):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     calls, stop, _ = eps_dev.read_progress()
+    if args.dump_outputs and rank == 0:
+        # per episode of this rank: MPC calls made and stop bits
+        dump_outputs(args.dump_outputs, {"calls": calls, "stop": stop})
     outs = [(None, "recursive_error" if st & MPC_EP_BREAK else
              "on_target" if st & MPC_EP_ARRIVED else "max_calls") for st in stop]
     robot_steps = int(calls.sum())
@@ -1833,7 +1963,7 @@ def bench_episodes(args, wl, eng, rank, world, cpu):
     flops = FT_FLOPS_PER_LEAF[args.integrator] * leaves / world / elapsed      # per GPU
     out = {
         "metric": METRIC, "value": leaves / elapsed, "unit": "leaves/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup,
+        "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": elapsed / max(1, lockstep) * 1e3,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
         "data": "synthetic (the script's seeded start/target draws)",

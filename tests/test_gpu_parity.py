@@ -1264,7 +1264,7 @@ def test_overlapped_exchange_with_a_late_collective(engine):
 
 @pytest.mark.parametrize("extra", [[], ["--integrator", "rect+rot"]])
 def test_bench_contract(extra):
-    """bench.py (a short run, no CPU leg) prints ONE JSON line with the
+    """bench.py --full (a short run, no CPU leg) prints ONE JSON line with the
     driver's contract keys; the default step is the chained rect+cum launch
     and its roofline is the chained kernel's, with the committed PMC traffic
     of that kernel; two-launch rect+rot reports the rollout kernel."""
@@ -1272,7 +1272,7 @@ def test_bench_contract(extra):
     import os
     import subprocess
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "8",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--steps", "8",
                         "--warmup", "2", "--cpu-seconds", "0", "--no-second-pass"] + extra,
                        capture_output=True, text=True, timeout=200, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -1334,10 +1334,10 @@ def test_bench_two_ranks_spawned(mode):
     import subprocess
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    # the driver's own form (--steps 20 --warmup 5, second input pass, parity
+    # the driver's --full form (--steps 20 --warmup 5, second input pass, parity
     # check and config-D sub-result included); gloo and a smaller config-C
     # shard only because both ranks share this one GPU
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--full",
                         "--dist-backend", "gloo", "--candidates-per-gpu", "100000", "--steps", "20",
                         "--warmup", "5", "--exchange-mode", mode],
                        capture_output=True, text=True, timeout=300, cwd=repo, env=env)
@@ -1376,19 +1376,74 @@ def test_bench_two_ranks_spawned(mode):
 
 
 def test_bench_workload_a_parity():
-    """bench.py --workload A: the reference scenario through the drop-in,
+    """bench.py --workload A --full: the reference scenario through the drop-in,
     one JSON line with every recorded call's chosen control identical."""
     import json
     import os
     import subprocess
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--workload", "A",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--workload", "A", "--full",
                         "--steps", "1", "--warmup", "0", "--cpu-seconds", "0"],
                        capture_output=True, text=True, timeout=200, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["parity"]["calls"] == 349 == d["parity"]["chosen_control_identical"]
     assert d["parity"]["max_abs_pose_diff"] <= 1e-6 and d["p50_ms"] > 0
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) times the K steps only — the line keeps the
+    headline keys, every field that needs a pass of its own is null — and
+    --dump-outputs writes what the timed steps returned: per step the log
+    record, and the last step's winner record, identical from run to run
+    (the ramp before the timed region is as long as the clock says, the
+    episode restarts a fixed number of steps before the timed ones)."""
+    import json
+    import os
+    import subprocess
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    k, n, ns = 8, 20_000, 10
+    dumps = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1",
+                            "--steps", str(k), "--warmup", "2", "--candidates-per-gpu", str(n),
+                            "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=200, cwd=repo)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["full"] is False and d["steps"] == k and d["dtype"] == "f64"
+        assert d["unit"] == "rollouts/s" and d["higher_is_better"] is True
+        assert d["ms_per_step"] > 0
+        assert abs(d["value"] / (n / (d["ms_per_step"] * 1e-3)) - 1) < 1e-9
+        for key in ("cpu_baseline", "roofline", "other_inputs", "generated_inputs", "p50_ms",
+                    "p50_host_ms", "kernel_ms"):
+            assert d[key] is None, key
+        assert "parity" not in d and "config_d" not in d
+        assert d["config"]["step_launches"].startswith("chained") and d["chain_error"] == 0
+        dumps.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["step_cost", "step_index", "step_state", "step_status",
+                                      "winner_control", "winner_cost", "winner_found",
+                                      "winner_index", "winner_trajectory"]
+    for name in a:
+        assert a[name].dtype == np.float64
+        assert np.array_equal(a[name], b[name], equal_nan=True), name
+    assert a["step_index"].shape == (k,) and a["step_state"].shape == (k, 5)
+    assert a["winner_trajectory"].shape == (ns, 3)
+    # the timed steps are steps K .. 2K-1 of the restarted episode
+    assert a["step_status"][:, 0].tolist() == list(range(k, 2 * k))
+    assert ((0 <= a["step_index"]) & (a["step_index"] < n)).all()
+    # the winner record is the last step's: its candidate, cost and first state
+    # (every step starts from the incumbent float(sys.maxsize), so a candidate
+    # is found; 2K steps of at most v_max * 0.05 leave the robot far from the
+    # target at distance 3.6, so the finishing logic returns layer 0)
+    assert a["winner_found"][0] == 1 and a["winner_index"][0] == a["step_index"][-1]
+    assert a["winner_cost"][0] == a["step_cost"][-1]
+    assert np.array_equal(a["winner_control"], a["step_state"][-1, 3:])
+    assert np.abs(a["winner_trajectory"][0] - a["step_state"][-1, :3]).max() <= 1e-12
 
 
 @pytest.mark.parametrize("integ,n,L", [("rect+cum", 100_000, None), ("rect+rot", 100_000, None),

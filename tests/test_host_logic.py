@@ -160,6 +160,53 @@ def test_bench_defaults(monkeypatch):
     assert (f.integrator, f.steps) == ("rect+rot", 50)
     assert parse("--integrator", "qk21").integrator == "qk21"
     assert parse("--inputs", "generated").inputs == "generated"
+    # a plain run times the steps only; --full adds every other measurement
+    assert a.full is False and a.dump_outputs is None
+    assert parse("--full").full is True
+    assert parse("--dump-outputs", "out").dump_outputs == "out"
+
+
+def test_bench_episode_outputs(tmp_path):
+    """--dump-outputs: the timed steps' log records (the K before the
+    snapshot's step count, whatever older steps the ring still holds) and the
+    winner record become float64 .npy arrays."""
+    import ctypes
+    import os
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    from diplomjourney_amd.abi import MpcEpisodeLog, MpcResult
+    cap, k, ns = 8, 3, 4
+    ring = (MpcEpisodeLog * cap)()
+    for step in (0, 1, 2, 3, 4, 5, 14, 15):      # 14, 15: left by an earlier, longer run
+        ring[step % cap] = MpcEpisodeLog(step, 100 + step, step + 1, 1, 1, 0, 0.5 * step,
+                                         1.0 * step, 2.0 * step, 3.0 * step, 0.25, -0.5)
+    w = MpcResult(cost=2.5, index=105, found=1, n_steps=ns, v=0.25, beta=-0.5)
+    for s in range(ns):
+        for c in range(3):
+            w.traj[s][c] = 10.0 * s + c
+    snap = {"steps_enqueued": 6, "log": bytes(ring), "winner": bytes(w)}
+    out = bench.episode_outputs(snap, k, ns)
+    assert out["step_index"].tolist() == [103, 104, 105]
+    assert out["step_cost"].tolist() == [1.5, 2.0, 2.5]
+    assert out["step_state"].tolist() == [[s, 2 * s, 3 * s, 0.25, -0.5] for s in (3.0, 4.0, 5.0)]
+    assert out["step_status"].tolist() == [[s, s + 1, 1, 1, 0] for s in (3, 4, 5)]
+    assert out["winner_index"] == [105] and out["winner_control"] == [0.25, -0.5]
+    assert out["winner_trajectory"] == [[10.0 * s + c for c in range(3)] for s in range(ns)]
+    # more timed steps than the ring holds: the last `cap` of them
+    full = (MpcEpisodeLog * cap)()
+    for step in range(12, 20):
+        full[step % cap] = MpcEpisodeLog(step, step, 1, 1, 1, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+    many = bench.episode_outputs({"steps_enqueued": 20, "log": bytes(full), "winner": None},
+                                 16, ns)
+    assert many["step_index"].tolist() == list(range(12, 20)) and "winner_index" not in many
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    got = {f: np.load(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")}
+    assert sorted(got) == sorted(n + ".npy" for n in out)
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["winner_trajectory.npy"].shape == (ns, 3)
+    assert got["step_index.npy"].tolist() == [103.0, 104.0, 105.0]
 
 
 def _bench(args, env_extra=None, drop=("WORLD_SIZE", "RANK", "LOCAL_RANK")):

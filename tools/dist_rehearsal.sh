@@ -10,8 +10,8 @@ mkdir -p $OUT
 export MASTER_ADDR=127.0.0.1
 # (no time-based ramp: every run logs the same first steps, which the
 # 8192-record log ring still holds)
-A="--cpu-seconds 0 --steps 40 --warmup 2 --dist-backend gloo --no-graph --no-second-pass --ramp-seconds 0"
-F="--workload F --cpu-seconds 0 --steps 6 --warmup 1 --dist-backend gloo"
+A="--full --cpu-seconds 0 --steps 40 --warmup 2 --dist-backend gloo --no-graph --no-second-pass --ramp-seconds 0"
+F="--full --workload F --cpu-seconds 0 --steps 6 --warmup 1 --dist-backend gloo"
 timeout -k 10 200 python bench.py $A --candidates-per-gpu 400000 --dump-log $OUT/w1.json > $OUT/w1.out 2>&1 && \
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py $A --gpus 2 --candidates-per-gpu 200000 --dump-log $OUT/w2.json > $OUT/w2.out 2>&1 && \
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29512 bench.py $A --gpus 4 --candidates-per-gpu 100000 --dump-log $OUT/w4.json > $OUT/w4.out 2>&1 && \

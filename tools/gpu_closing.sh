@@ -35,16 +35,16 @@ pmc chain_p2p_tiled "1000000 10 p2p 20 4" 160e6 "k_episode_chain<1, 2, 4" "k_epi
 step valu 900 bash -c "TAG=${TAG:-closing}/valu bash tools/pmc_valu.sh > $OUT/valu.log 2>&1"
 fi
 if [ "${PART:-2}" = 2 ]; then
-step bench 300 bash -c "python bench.py > $OUT/bench.json 2> $OUT/bench.err"
-step bench_driver 300 bash -c "python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err"
-step rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/rocprof -o run -- python3 bench.py --cpu-seconds 0 --no-second-pass --no-config-d --parity-steps 0
+step bench 300 bash -c "python bench.py --full > $OUT/bench.json 2> $OUT/bench.err"
+step bench_driver 300 bash -c "python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err"
+step rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/rocprof -o run -- python3 bench.py --full --cpu-seconds 0 --no-second-pass --no-config-d --parity-steps 0
 find $OUT/rocprof -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_C.csv \;
 for w in B D A R F G E; do
-  step bench_$w 300 bash -c "python bench.py --cpu-seconds 0 --no-second-pass --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err"
+  step bench_$w 300 bash -c "python bench.py --full --cpu-seconds 0 --no-second-pass --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err"
 done
-step bench_qk21 300 bash -c "python bench.py --cpu-seconds 0 --no-second-pass --parity-steps 0 --no-config-d --integrator qk21 > $OUT/bench_qk21.json 2> $OUT/bench_qk21.err"
-step bench_exchange 300 bash -c "python bench.py --cpu-seconds 0 --no-second-pass --parity-steps 0 --no-config-d --exchange > $OUT/bench_exchange.json 2> $OUT/bench_exchange.err"
-step bench_exchange_rccl 300 bash -c "python bench.py --cpu-seconds 0 --no-second-pass --parity-steps 0 --no-config-d --exchange --exchange-mode rccl > $OUT/bench_exchange_rccl.json 2> $OUT/bench_exchange_rccl.err"
-step overlap_exit 300 bash -c "rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $OUT/overlap_exit -o run -- python3 bench.py --exchange --overlap-exchange --cpu-seconds 0 --no-second-pass --parity-steps 0 --no-config-d --steps 20 --warmup 5 > $OUT/overlap_exit.log 2>&1"
+step bench_qk21 300 bash -c "python bench.py --full --cpu-seconds 0 --no-second-pass --parity-steps 0 --no-config-d --integrator qk21 > $OUT/bench_qk21.json 2> $OUT/bench_qk21.err"
+step bench_exchange 300 bash -c "python bench.py --full --cpu-seconds 0 --no-second-pass --parity-steps 0 --no-config-d --exchange > $OUT/bench_exchange.json 2> $OUT/bench_exchange.err"
+step bench_exchange_rccl 300 bash -c "python bench.py --full --cpu-seconds 0 --no-second-pass --parity-steps 0 --no-config-d --exchange --exchange-mode rccl > $OUT/bench_exchange_rccl.json 2> $OUT/bench_exchange_rccl.err"
+step overlap_exit 300 bash -c "rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $OUT/overlap_exit -o run -- python3 bench.py --full --exchange --overlap-exchange --cpu-seconds 0 --no-second-pass --parity-steps 0 --no-config-d --steps 20 --warmup 5 > $OUT/overlap_exit.log 2>&1"
 fi
 echo "[closing] done" >&2

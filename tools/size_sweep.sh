@@ -8,7 +8,7 @@ mkdir -p $O
 : > $O/sweep.jsonl
 for spec in 250000:500 500000:500 1000000:500 2000000:400 4000000:200 8000000:100; do
   n=${spec%%:*}; k=${spec##*:}
-  timeout -k 10 240 python bench.py --cpu-seconds 0 --no-second-pass --candidates-per-gpu $n \
+  timeout -k 10 240 python bench.py --full --cpu-seconds 0 --no-second-pass --candidates-per-gpu $n \
     --steps $k --warmup 20 >> $O/sweep.jsonl 2> $O/sweep_$n.err || exit 1
 done
 python - <<'PY'
