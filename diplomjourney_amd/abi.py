@@ -49,6 +49,24 @@ class MpcProblem(ctypes.Structure):
         return tuple(getattr(self, n) for n, _ in self._fields_)
 
 
+MPC_MAX_OBSTACLES = 16
+
+
+class MpcObstacle(ctypes.Structure):
+    """mpc_obstacle_t: one keep-out circle in world coordinates."""
+    _fields_ = [("x", ctypes.c_double), ("y", ctypes.c_double), ("r", ctypes.c_double)]
+
+
+def make_obstacles(obstacles):
+    """(MpcObstacle array or None, count) of a sequence of (x, y, r)."""
+    obs = [tuple(float(q) for q in o) for o in (obstacles or ())]
+    if any(len(o) != 3 for o in obs):
+        raise ValueError("an obstacle is (x, y, r)")
+    if not obs:
+        return None, 0
+    return (MpcObstacle * len(obs))(*[MpcObstacle(*o) for o in obs]), len(obs)
+
+
 class MpcResult(ctypes.Structure):
     """mpc_result_t: the selected candidate and its per-step states."""
     _fields_ = [

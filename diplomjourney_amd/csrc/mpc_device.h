@@ -232,6 +232,90 @@ MPC_HD __forceinline__ double cost(double x, double y, const Consts& K) {
   return 10000.0 * dist_target + 10000.0 * (d * d);            // :62, :87
 }
 
+// Keep-out circles (mpc_rollout_partials_obstacles; semantics in
+// include/mpc_rollout.h).  One table per launch, a kernel argument: every
+// entry is wave-uniform and reaches the test as a scalar operand, nothing per
+// lane.  Entries past the call's count hold r2 = -1, which no squared distance
+// is below, so a kernel instantiated for NOBS circles serves any count <= NOBS
+// with straight-line code.
+//   loop:  the circles in the frame of the step recurrence's (x, y): world
+//          coordinates, or for kRotCum the start-pose frame of the sums (A, B)
+//          — centres rotated by -phi about the start position, and with the
+//          1/L-scaled sums of PL2 centres and radii scaled by 1/L (exact: L is
+//          a power of two) — so the test needs no cum_pose per step.
+//   world: world coordinates, for the irregular-candidate recompute
+//          (step_safe), whose states replace the loop's.
+struct Circle {
+  double cx, cy, r2, pad_;   // 32 B
+};
+struct Obstacles {
+  Circle c[MPC_MAX_OBSTACLES];
+};
+struct ObstacleArgs {
+  Obstacles loop, world;
+};
+// The table as the kernels read it: in the kernel-argument segment (constant
+// address space: scalar loads).
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) Obstacles* ObsTable;
+#else
+typedef const Obstacles* ObsTable;
+#endif
+
+// Obstacle hooks of the rollout lanes (the style of NoPre / NoSide): loop()
+// after every step of the step_core recurrence, for the lane's CPL candidates
+// together (one read of the table); world() after every step of the step_safe
+// recompute.  Both OR into the candidates' `blocked` flags, which sit next to
+// `bad`.  NoObs: the kernels without obstacles (no obstacle statement is
+// instantiated: their code is unchanged).
+struct NoObs {
+  static constexpr bool kOn = false;
+};
+
+// (x, y) strictly inside any of the first NOBS circles.  Predicates only: no
+// branch, no early exit; a NaN state compares false (its NaN cost never wins
+// anyway).  Per circle and candidate 2 add, 1 mul, 1 fma, 1 compare; the lane
+// masks are combined on the SALU.
+// Up to 4 circles (24 SGPRs) stay in SGPRs across the rollout loop.  16 would
+// need 96 of the ~100 SGPRs: hipcc hoists the loads out of the loop all the
+// same and spills them to VGPR lanes, and the loop then reloads every operand
+// with a v_readlane (146-171 of ~400 VALU per lane-step, counted in the ISA).
+// So for NOBS > 4 the table pointer is made opaque per step: the step's
+// scalar loads stay inside the step (32 s_load per lane-step, no VALU).
+template <int NOBS>
+struct CircleObs {
+  static_assert(NOBS >= 1 && NOBS <= MPC_MAX_OBSTACLES, "circle count");
+  static constexpr bool kOn = true;
+  ObsTable loop_t, world_t;
+  template <int CPL>
+  __device__ __forceinline__ static void test(ObsTable t, const double (&x)[CPL],
+                                              const double (&y)[CPL], bool (&blocked)[CPL]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (NOBS > 4) asm volatile("" : "+s"(t));
+#endif
+#pragma unroll
+    for (int i = 0; i < NOBS; ++i) {
+      const double cx = t->c[i].cx, cy = t->c[i].cy, r2 = t->c[i].r2;
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) {
+        const double dx = x[j] - cx, dy = y[j] - cy;
+        blocked[j] |= fma(dy, dy, dx * dx) < r2;
+      }
+    }
+  }
+  template <int CPL>
+  __device__ __forceinline__ void loop(const double (&x)[CPL], const double (&y)[CPL],
+                                       bool (&blocked)[CPL]) const {
+    test<CPL>(loop_t, x, y, blocked);
+  }
+  __device__ __forceinline__ void world(double x, double y, bool& blocked) const {
+    const double xs[1] = {x}, ys[1] = {y};
+    bool bl[1] = {blocked};
+    test<1>(world_t, xs, ys, bl);
+    blocked = bl[0];
+  }
+};
+
 // One candidate, exactly as the kernels evaluate it (the host replica in
 // tests/replica_harness.cpp calls this): the core recurrence, and if that
 // flags the candidate, the safe recurrence.  traj (optional) gets the

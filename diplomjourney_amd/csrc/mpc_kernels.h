@@ -118,11 +118,15 @@ __device__ __forceinline__ Consts uniform_consts(const Consts& k) {
 }
 
 // Rollout of CPL adjacent candidates starting at column c0; costs in cst.
-template <int CPL, int INTEG, int ROT, bool STATES, bool PL2>
+// obs: the obstacle hook (NoObs: none); blocked_out[CPL] (Obs::kOn only):
+// the candidates that entered a keep-out circle.
+template <int CPL, int INTEG, int ROT, bool STATES, bool PL2, class Obs = NoObs>
 __device__ __forceinline__ void rollout_lane_l(const Consts& K, const double* __restrict__ v,
                                              const double* __restrict__ b, int64_t ld, int64_t c0,
                                              int n_steps, double (&cst)[CPL],
-                                             double* __restrict__ states, int64_t n_cand) {
+                                             double* __restrict__ states, int64_t n_cand,
+                                             const Obs& obs = Obs{},
+                                             bool* blocked_out = nullptr) {
   double x[CPL], y[CPL], ph[CPL], sn[CPL], cs[CPL];
 #pragma unroll
   for (int j = 0; j < CPL; ++j) step_start<ROT>(K, x[j], y[j], ph[j], sn[j], cs[j]);
@@ -145,8 +149,12 @@ __device__ __forceinline__ void rollout_lane_l(const Consts& K, const double* __
     }
   };
   bool bad[CPL];
+  [[maybe_unused]] bool blocked[CPL];
 #pragma unroll
-  for (int j = 0; j < CPL; ++j) bad[j] = false;
+  for (int j = 0; j < CPL; ++j) {
+    bad[j] = false;
+    if constexpr (Obs::kOn) blocked[j] = false;
+  }
   auto body = [&](int sr, const double (&vv)[CPL], const double (&bb)[CPL]) {
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
@@ -159,6 +167,7 @@ __device__ __forceinline__ void rollout_lane_l(const Consts& K, const double* __
         states[(sr * 3 + 2) * n_cand + c0 + j] = ph[j];
       }
     }
+    if constexpr (Obs::kOn) obs.loop(x, y, blocked);
   };
   // Software pipeline: the controls of the next kPrefetch-1 steps are in
   // flight while this step's trig chain runs (rotating register buffers,
@@ -193,8 +202,10 @@ __device__ __forceinline__ void rollout_lane_l(const Consts& K, const double* __
       x[j] = K.x;
       y[j] = K.y;
       ph[j] = K.phi;
+      if constexpr (Obs::kOn) blocked[j] = false;   // the recompute's states replace the loop's
       for (int sr = 0; sr < n_steps; ++sr) {
         step_safe<INTEG>(x[j], y[j], ph[j], v[sr * ld + c0 + j], b[sr * ld + c0 + j], K);
+        if constexpr (Obs::kOn) obs.world(x[j], y[j], blocked[j]);
         if constexpr (STATES) {
           states[(sr * 3 + 0) * n_cand + c0 + j] = x[j];
           states[(sr * 3 + 1) * n_cand + c0 + j] = y[j];
@@ -203,6 +214,7 @@ __device__ __forceinline__ void rollout_lane_l(const Consts& K, const double* __
       }
     }
     cst[j] = cost(x[j], y[j], K);
+    if constexpr (Obs::kOn) blocked_out[j] = blocked[j];
   }
 }
 
@@ -317,15 +329,18 @@ struct NoPre {
 // issues complete with that step's last control DMA (the tail waits for both).
 // PIN: the leading trig coefficients pinned in VGPRs (8 VGPRs for ~8 VALU per
 // lane-step); off where the register budget is tighter than the VALU budget.
+// obs / blocked_out[2]: as in rollout_lane_l.
 template <int INTEG, int ROT, bool PL2, class Pre = NoPre, class Pre0 = NoPre,
-          class Mid = NoPre, bool PIN = true>
+          class Mid = NoPre, bool PIN = true, class Obs = NoObs>
 __device__ __forceinline__ void rollout_lane_glds_k(const Consts& K, const Consts& Kloop,
                                                     const double* __restrict__ v,
                                                     const double* __restrict__ b, int64_t ld,
                                                     int64_t c0, int n_steps, double (&cst)[2],
                                                     const Pre& pre = Pre{},
                                                     const Pre0& pre0 = Pre0{},
-                                                    const Mid& mid = Mid{}) {
+                                                    const Mid& mid = Mid{},
+                                                    const Obs& obs = Obs{},
+                                                    bool* blocked_out = nullptr) {
   constexpr int CPL = 2;
   constexpr int R = kRing;
   const int lane = threadIdx.x & 63;
@@ -349,6 +364,7 @@ __device__ __forceinline__ void rollout_lane_glds_k(const Consts& K, const Const
   Consts KL;
   double x[CPL], y[CPL], ph[CPL], sn[CPL], cs[CPL];
   bool bad[CPL];
+  [[maybe_unused]] bool blocked[CPL];
   for (int pass = 0;; ++pass) {
 #pragma unroll
     for (int u = 0; u < R - 1; ++u)
@@ -364,6 +380,7 @@ __device__ __forceinline__ void rollout_lane_glds_k(const Consts& K, const Const
     for (int j = 0; j < CPL; ++j) {
       step_start<ROT>(KL, x[j], y[j], ph[j], sn[j], cs[j]);
       bad[j] = false;
+      if constexpr (Obs::kOn) blocked[j] = false;
     }
     double2 v2 = make_double2(0.0, 0.0), b2 = v2;   // the last slot's contents as read
 #pragma unroll 1
@@ -392,6 +409,7 @@ __device__ __forceinline__ void rollout_lane_glds_k(const Consts& K, const Const
                                      &lead);
           step_core<INTEG, ROT, PL2>(x[1], y[1], ph1, sn[1], cs[1], v2.y, b2.y, KL, bad[1],
                                      &lead);
+          if constexpr (Obs::kOn) obs.loop(x, y, blocked);
           if (!ROT) {
             ph[0] = ph0;
             ph[1] = ph1;
@@ -433,61 +451,94 @@ __device__ __forceinline__ void rollout_lane_glds_k(const Consts& K, const Const
         x[j] = Ks.x;
         y[j] = Ks.y;
         ph[j] = Ks.phi;
-        for (int sr = 0; sr < n_steps; ++sr)
+        if constexpr (Obs::kOn) blocked[j] = false;   // the recompute's states replace the loop's
+        for (int sr = 0; sr < n_steps; ++sr) {
           step_safe<INTEG>(x[j], y[j], ph[j], v[sr * ld + c0 + j], b[sr * ld + c0 + j], Ks);
+          if constexpr (Obs::kOn) obs.world(x[j], y[j], blocked[j]);
+        }
         cst[j] = cost(x[j], y[j], Ks);
       }
     }
+  }
+  if constexpr (Obs::kOn) {
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) blocked_out[j] = blocked[j];
   }
 }
 
 // kRotCum keeps the start pose's terms live across the loop: with pinned
 // leads it needs > 96 VGPRs and spills at 5 waves/SIMD (any scratch costs far
 // more than the fifth wave gains), unpinned it fits.
-template <int INTEG, int ROT, bool PL2>
+template <int INTEG, int ROT, bool PL2, class Obs = NoObs>
 __device__ __forceinline__ void rollout_lane_glds(const Consts& K, const double* __restrict__ v,
                                                   const double* __restrict__ b, int64_t ld,
-                                                  int64_t c0, int n_steps, double (&cst)[2]) {
-  rollout_lane_glds_k<INTEG, ROT, PL2, NoPre, NoPre, NoPre, ROT != kRotCum>(
-      K, K, v, b, ld, c0, n_steps, cst);
+                                                  int64_t c0, int n_steps, double (&cst)[2],
+                                                  const Obs& obs = Obs{},
+                                                  bool* blocked_out = nullptr) {
+  rollout_lane_glds_k<INTEG, ROT, PL2, NoPre, NoPre, NoPre, ROT != kRotCum, Obs>(
+      K, K, v, b, ld, c0, n_steps, cst, NoPre{}, NoPre{}, NoPre{}, obs, blocked_out);
 }
 
 // L a power of two or not: one loop body each (see step_core).
-template <int CPL, int INTEG, int ROT, bool STATES>
+template <int CPL, int INTEG, int ROT, bool STATES, class Obs = NoObs>
 __device__ __forceinline__ void rollout_lane(const Consts& K, const double* __restrict__ v,
                                              const double* __restrict__ b, int64_t ld, int64_t c0,
                                              int n_steps, double (&cst)[CPL],
-                                             double* __restrict__ states, int64_t n_cand) {
+                                             double* __restrict__ states, int64_t n_cand,
+                                             const Obs& obs = Obs{},
+                                             bool* blocked_out = nullptr) {
   if constexpr (CPL == 2 && !STATES) {
     if (K.L_pow2)
-      rollout_lane_glds<INTEG, ROT, true>(K, v, b, ld, c0, n_steps, cst);
+      rollout_lane_glds<INTEG, ROT, true, Obs>(K, v, b, ld, c0, n_steps, cst, obs, blocked_out);
     else
-      rollout_lane_glds<INTEG, ROT, false>(K, v, b, ld, c0, n_steps, cst);
+      rollout_lane_glds<INTEG, ROT, false, Obs>(K, v, b, ld, c0, n_steps, cst, obs, blocked_out);
     return;
   }
   if (K.L_pow2)
-    rollout_lane_l<CPL, INTEG, ROT, STATES, true>(K, v, b, ld, c0, n_steps, cst, states, n_cand);
+    rollout_lane_l<CPL, INTEG, ROT, STATES, true, Obs>(K, v, b, ld, c0, n_steps, cst, states,
+                                                       n_cand, obs, blocked_out);
   else
-    rollout_lane_l<CPL, INTEG, ROT, STATES, false>(K, v, b, ld, c0, n_steps, cst, states, n_cand);
+    rollout_lane_l<CPL, INTEG, ROT, STATES, false, Obs>(K, v, b, ld, c0, n_steps, cst, states,
+                                                        n_cand, obs, blocked_out);
 }
 
-template <int CPL, int INTEG, int ROT, bool STATES, bool KDEV>
+// The waves' blocked-candidate counts of the obstacle variants (LDS only in
+// the kernels that call this).
+__device__ __forceinline__ uint32_t* blocked_slots() {
+  __shared__ uint32_t s_blocked[kWaves];
+  return s_blocked;
+}
+
+// Obs::kOn: a blocked candidate takes the key of a non-finite cost (~0: never
+// wins), so the block records and everything downstream of them are those of
+// the kernels without obstacles; n_blocked (nullable) gets the number of
+// blocked candidates — a ballot popcount per wave and candidate slot, one
+// 64-bit atomic add per block.
+template <int CPL, int INTEG, int ROT, bool STATES, bool KDEV, class Obs = NoObs>
 __device__ __forceinline__ void rollout_argmin_body(
     const Consts& Karg, const Consts* __restrict__ Kdev, const double* __restrict__ v,
     const double* __restrict__ b, int64_t n_cand, int n_steps, Rec* __restrict__ part,
-    double* __restrict__ states) {
+    double* __restrict__ states, const Obs& obs = Obs{},
+    unsigned long long* __restrict__ n_blocked = nullptr) {
   const Consts K = KDEV ? *Kdev : Karg;
   const int64_t n_tiles = (n_cand + kBlock * CPL - 1) / (kBlock * CPL);
   uint64_t best_k = ~0ull;
   int64_t best_i = INT64_MAX;
+  [[maybe_unused]] uint32_t wave_blocked = 0;   // (wave-uniform)
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t c0 = tile * (kBlock * CPL) + threadIdx.x * CPL;
     if (c0 < n_cand) {  // CPL > 1 requires n_cand % CPL == 0: the whole group is valid
       double cst[CPL];
-      rollout_lane<CPL, INTEG, ROT, STATES>(K, v, b, n_cand, c0, n_steps, cst, states, n_cand);
+      [[maybe_unused]] bool blocked[CPL];
+      rollout_lane<CPL, INTEG, ROT, STATES, Obs>(K, v, b, n_cand, c0, n_steps, cst, states,
+                                                 n_cand, obs, blocked);
 #pragma unroll
       for (int j = 0; j < CPL; ++j) {
-        const uint64_t kk = cost_key_nonneg(cst[j]);
+        uint64_t kk = cost_key_nonneg(cst[j]);
+        if constexpr (Obs::kOn) {
+          kk = blocked[j] ? ~0ull : kk;
+          wave_blocked += __builtin_popcountll(__builtin_amdgcn_ballot_w64(blocked[j]));
+        }
         if (kk < best_k) {  // ascending index per lane: strict < keeps the first
           best_k = kk;
           best_i = c0 + j;
@@ -495,8 +546,19 @@ __device__ __forceinline__ void rollout_argmin_body(
       }
     }
   }
+  if constexpr (Obs::kOn) {
+    if ((threadIdx.x & 63) == 0) blocked_slots()[threadIdx.x >> 6] = wave_blocked;
+  }   // (block_argmin's barrier orders these stores before thread 0's reads)
   block_argmin<CPL == kCplWide>(best_k, best_i);   // (wide path: rows < 2^28 candidates)
   if (threadIdx.x == 0) part[blockIdx.x] = Rec{best_k, best_i};
+  if constexpr (Obs::kOn) {
+    if (threadIdx.x == 0 && n_blocked) {
+      uint32_t total = 0;
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) total += blocked_slots()[w];
+      if (total) atomicAdd(n_blocked, static_cast<unsigned long long>(total));
+    }
+  }
 }
 
 // Scalar (CPL = 1), CoordinateTree-states and register-ring paths.
@@ -520,6 +582,43 @@ __global__ __launch_bounds__(kBlock, kStreamWaves) void k_rollout_argmin_stream(
     const double* __restrict__ b, int64_t n_cand, int n_steps, Rec* __restrict__ part) {
   rollout_argmin_body<kCplWide, INTEG, ROT, false, KDEV>(Karg, Kdev, v, b, n_cand, n_steps,
                                                           part, nullptr);
+}
+
+// The obstacle variants (mpc_rollout_partials_obstacles): the same bodies with
+// the CircleObs<NOBS> hook.  The circle tables are the kernels' FIRST argument
+// `O`, i.e. offset 0 of the kernel-argument segment, and are read through the
+// segment pointer (constant address space, scalar loads; see CircleObs for why
+// not through the by-value parameter).
+// kObsStreamWaves: the launch bound of the streaming variant.
+template <int NOBS>
+__device__ __forceinline__ CircleObs<NOBS> kernarg_obs() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const auto* a = (const __attribute__((address_space(4))) ObstacleArgs*)
+      __builtin_amdgcn_kernarg_segment_ptr();
+  return CircleObs<NOBS>{&a->loop, &a->world};
+#else
+  return CircleObs<NOBS>{nullptr, nullptr};   // (the host pass only parses the kernels)
+#endif
+}
+
+template <int CPL, int INTEG, int ROT, bool STATES, int NOBS>
+__global__ __launch_bounds__(kBlock, 1) void k_rollout_argmin_obs(
+    ObstacleArgs O, Consts Karg, const double* __restrict__ v, const double* __restrict__ b,
+    int64_t n_cand, int n_steps, Rec* __restrict__ part, double* __restrict__ states,
+    unsigned long long* __restrict__ n_blocked) {
+  rollout_argmin_body<CPL, INTEG, ROT, STATES, false>(Karg, nullptr, v, b, n_cand, n_steps, part,
+                                                       states, kernarg_obs<NOBS>(), n_blocked);
+}
+
+constexpr int kObsStreamWaves = 5;
+template <int INTEG, int ROT, int NOBS>
+__global__ __launch_bounds__(kBlock, kObsStreamWaves) void k_rollout_argmin_stream_obs(
+    ObstacleArgs O, Consts Karg, const double* __restrict__ v, const double* __restrict__ b,
+    int64_t n_cand, int n_steps, Rec* __restrict__ part,
+    unsigned long long* __restrict__ n_blocked) {
+  rollout_argmin_body<kCplWide, INTEG, ROT, false, false>(Karg, nullptr, v, b, n_cand, n_steps,
+                                                           part, nullptr, kernarg_obs<NOBS>(),
+                                                           n_blocked);
 }
 
 // Measurement probe (mpc_stream_probe): the streaming kernel's memory side

@@ -239,6 +239,68 @@ void launch_rollout(hipStream_t st, int32_t integrator, const Consts& K, const C
   });
 }
 
+// Keep-out circles (mpc_rollout_partials_obstacles).
+int check_obstacles(const mpc_obstacle_t* obs, int32_t n) {
+  if (n < 0 || n > MPC_MAX_OBSTACLES || (n > 0 && !obs)) return MPC_ERR_ARG;
+  for (int i = 0; i < n; ++i)
+    if (!isfinite(obs[i].x) || !isfinite(obs[i].y) || !isfinite(obs[i].r) || !(obs[i].r > 0))
+      return MPC_ERR_ARG;
+  return MPC_OK;
+}
+
+// The launch's circle tables (mpc_device.h Obstacles): `world` as given;
+// `loop` in the frame of the recurrence's (x, y) — for kRotCum the centres in
+// the start-pose frame, A = c0 dx + s0 dy, B = c0 dy - s0 dx with (dx, dy) the
+// centre minus the start position (the inverse of cum_pose), and for the
+// 1/L-scaled sums (L a power of two) centres and radius times 1/L.  Entries
+// past n can never be entered (r2 = -1).
+ObstacleArgs host_obstacles(const Consts& K, const mpc_obstacle_t* obs, int n, bool cum) {
+  ObstacleArgs O;
+  for (int i = 0; i < MPC_MAX_OBSTACLES; ++i) O.world.c[i] = Circle{0.0, 0.0, -1.0, 0.0};
+  for (int i = 0; i < n; ++i) O.world.c[i] = Circle{obs[i].x, obs[i].y, obs[i].r * obs[i].r, 0.0};
+  O.loop = O.world;
+  if (cum) {
+    const double sc = K.L_pow2 ? K.inv_L : 1.0;
+    for (int i = 0; i < n; ++i) {
+      const double dx = obs[i].x - K.x, dy = obs[i].y - K.y, r = obs[i].r * sc;
+      O.loop.c[i] = Circle{(K.c0 * dx + K.s0 * dy) * sc, (K.c0 * dy - K.s0 * dx) * sc, r * r, 0.0};
+    }
+  }
+  return O;
+}
+
+// The obstacle variant of launch_rollout / the states launch: the same grid
+// and path choice (so partial_count holds), instantiated for 1, 4 or
+// MPC_MAX_OBSTACLES circles on the streaming path and for MPC_MAX_OBSTACLES on
+// the one-candidate-per-lane paths.
+void launch_rollout_obs(hipStream_t st, int32_t integrator, const Consts& K, const ObstacleArgs& O,
+                        int n_obs, const double* v, const double* b, int64_t n_cand, int n_steps,
+                        Rec* part, double* states, unsigned long long* n_blocked) {
+  const bool wide = !states && wide_ok(v, b, n_cand);
+  dispatch_mode(integrator, [&](auto integ, auto rot) {
+    constexpr int I = decltype(integ)::value;
+    constexpr int R = decltype(rot)::value;
+    constexpr int kAll = MPC_MAX_OBSTACLES;
+    const dim3 g1(static_cast<unsigned>(rollout_grid<1>(n_cand)));
+    const dim3 g2(static_cast<unsigned>(rollout_grid<kCplWide>(n_cand)));
+    if (states)
+      k_rollout_argmin_obs<1, I, R, true, kAll><<<g1, kBlock, 0, st>>>(
+          O, K, v, b, n_cand, n_steps, part, states, n_blocked);
+    else if (!wide)
+      k_rollout_argmin_obs<1, I, R, false, kAll><<<g1, kBlock, 0, st>>>(
+          O, K, v, b, n_cand, n_steps, part, nullptr, n_blocked);
+    else if (n_obs <= 1)
+      k_rollout_argmin_stream_obs<I, R, 1><<<g2, kBlock, 0, st>>>(O, K, v, b, n_cand, n_steps,
+                                                                  part, n_blocked);
+    else if (n_obs <= 4)
+      k_rollout_argmin_stream_obs<I, R, 4><<<g2, kBlock, 0, st>>>(O, K, v, b, n_cand, n_steps,
+                                                                  part, n_blocked);
+    else
+      k_rollout_argmin_stream_obs<I, R, kAll><<<g2, kBlock, 0, st>>>(O, K, v, b, n_cand, n_steps,
+                                                                     part, n_blocked);
+  });
+}
+
 template <bool KDEV>
 void launch_finalize(hipStream_t st, int32_t integrator, const Rec* part, int n_part,
                      const Consts& K, const Consts* Kdev, const double* v, const double* b,
@@ -353,6 +415,45 @@ int mpc_rollout_argmin(const mpc_problem_t* p, const double* v_sc, const double*
   if (!out || index_base < 0) return MPC_ERR_ARG;
   const int a = mpc_rollout_partials(p, v_sc, beta_sc, n_cand, n_steps, integrator, states_out,
                                      ws, ws_bytes, stream);
+  if (a != MPC_OK) return a;
+  return mpc_rollout_finalize(p, v_sc, beta_sc, n_cand, n_steps, index_base, incumbent,
+                              integrator, states_out != nullptr, ws, ws_bytes, out, stream);
+}
+
+int mpc_rollout_partials_obstacles(const mpc_problem_t* p, const mpc_obstacle_t* obstacles,
+                                   int32_t n_obstacles, const double* v_sc,
+                                   const double* beta_sc, int64_t n_cand, int32_t n_steps,
+                                   int32_t integrator, double* states_out, void* ws,
+                                   size_t ws_bytes, int64_t* n_blocked_out, mpc_stream_t stream) {
+  const int a = check_args(p, v_sc, beta_sc, n_cand, n_steps, integrator, ws, ws_bytes);
+  if (a != MPC_OK) return a;
+  const int o = check_obstacles(obstacles, n_obstacles);
+  if (o != MPC_OK) return o;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (n_blocked_out &&
+      hipMemsetAsync(n_blocked_out, 0, sizeof(*n_blocked_out), st) != hipSuccess)
+    return MPC_ERR_HIP;
+  if (n_obstacles == 0)   // the kernels without obstacles: nothing can be blocked
+    return mpc_rollout_partials(p, v_sc, beta_sc, n_cand, n_steps, integrator, states_out, ws,
+                                ws_bytes, stream);
+  const Consts K = host_consts(*p);
+  const ObstacleArgs O = host_obstacles(K, obstacles, n_obstacles, is_cum(integrator));
+  launch_rollout_obs(st, integrator, K, O, n_obstacles, v_sc, beta_sc, n_cand, n_steps,
+                     static_cast<Rec*>(ws), states_out,
+                     reinterpret_cast<unsigned long long*>(n_blocked_out));
+  return last_hip_status();
+}
+
+int mpc_rollout_argmin_obstacles(const mpc_problem_t* p, const mpc_obstacle_t* obstacles,
+                                 int32_t n_obstacles, const double* v_sc, const double* beta_sc,
+                                 int64_t n_cand, int32_t n_steps, int64_t index_base,
+                                 double incumbent, int32_t integrator, double* states_out,
+                                 void* ws, size_t ws_bytes, int64_t* n_blocked_out,
+                                 mpc_result_t* out, mpc_stream_t stream) {
+  if (!out || index_base < 0) return MPC_ERR_ARG;
+  const int a = mpc_rollout_partials_obstacles(p, obstacles, n_obstacles, v_sc, beta_sc, n_cand,
+                                               n_steps, integrator, states_out, ws, ws_bytes,
+                                               n_blocked_out, stream);
   if (a != MPC_OK) return a;
   return mpc_rollout_finalize(p, v_sc, beta_sc, n_cand, n_steps, index_base, incumbent,
                               integrator, states_out != nullptr, ws, ws_bytes, out, stream);

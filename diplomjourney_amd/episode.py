@@ -59,9 +59,11 @@ class ChainError(RuntimeError):
 class Episode:
     def __init__(self, engine, n_cand_total, n_steps, rank=0, world=1, seed=20261015,
                  integrator="rect", group=None, start=(0.0, 0.0, 0.0, 0.0, 0.0), target=(2, 3),
-                 max_steps=0):
+                 max_steps=0, obstacles=()):
         self.eng = engine
         self.max_steps = int(max_steps)
+        # keep-out circles (x, y, r): candidates that enter one never win
+        self.obstacles = [tuple(o) for o in obstacles]
         # module globals of the reference that outlive an episode: the last
         # winner's layer states, result_v, result_beta (None: the initial
         # [[[0]]], which has no layer states)
@@ -134,7 +136,7 @@ class Episode:
             events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         if events:
             events[0].record()
-        self.eng.partials(prob, self.v_sc, self.b_sc, self.integrator)
+        self.eng.partials(prob, self.v_sc, self.b_sc, self.integrator, obstacles=self.obstacles)
         if events:
             events[1].record()
         out = self.eng.finalize(prob, self.v_sc, self.b_sc, index_base=self.lo,

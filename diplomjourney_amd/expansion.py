@@ -13,7 +13,7 @@ import torch
 
 from . import native
 from .abi import (INTEGRATORS, MPC_MAX_STEPS, RESULT_BYTES, PROBLEM_BYTES, MpcProblem,
-                  MpcResult, result_from_bytes)
+                  MpcResult, make_obstacles, result_from_bytes)
 
 
 def _stream_ptr():
@@ -24,6 +24,16 @@ def _integ(name_or_id):
     if isinstance(name_or_id, str):
         return INTEGRATORS[name_or_id]
     return int(name_or_id)
+
+
+def _blocked_ptr(n_blocked):
+    """Device pointer of the optional blocked-candidate counter (one int64)."""
+    if n_blocked is None:
+        return None
+    if not (isinstance(n_blocked, torch.Tensor) and n_blocked.is_cuda
+            and n_blocked.dtype == torch.int64 and n_blocked.numel() == 1):
+        raise TypeError("n_blocked must be a CUDA(HIP) int64 tensor of one element")
+    return n_blocked.data_ptr()
 
 
 def _check_soa(t, name, n_steps=None, n_cand=None):
@@ -57,11 +67,17 @@ class Expansion:
 
     # -- single problem --------------------------------------------------------
     def rollout_argmin(self, problem: MpcProblem, v_sc, beta_sc, index_base=0,
-                       incumbent=math.inf, integrator="qk21", states=None, out=None):
+                       incumbent=math.inf, integrator="qk21", states=None, out=None,
+                       obstacles=None, n_blocked=None):
         """Enqueue the expansion of one problem; returns the device result buffer.
 
         states: optional float64 tensor [n_steps, 3, n_cand] receiving every
         candidate's (x, y, phi) after every step (the CoordinateTree payload).
+        obstacles: optional sequence of keep-out circles (x, y, r): a candidate
+        whose state after any step lies inside one never wins
+        (mpc_rollout_argmin_obstacles).  n_blocked: optional int64 device
+        tensor [1] receiving the number of such candidates.  Without either,
+        the call is mpc_rollout_argmin.
         """
         _check_soa(v_sc, "v_sc")
         n_steps, n_cand = v_sc.shape
@@ -75,6 +91,16 @@ class Expansion:
         out = self.result if out is None else out
         ws_bytes = self.lib.mpc_workspace_bytes(n_cand, n_steps)
         ws = self._workspace(ws_bytes)
+        obs, n_obs = make_obstacles(obstacles)
+        if n_obs or n_blocked is not None:
+            st = self.lib.mpc_rollout_argmin_obstacles(
+                ctypes.byref(problem), obs, n_obs, v_sc.data_ptr(), beta_sc.data_ptr(), n_cand,
+                n_steps, int(index_base), float(incumbent), _integ(integrator),
+                states.data_ptr() if states is not None else None,
+                ws.data_ptr(), ws.numel(), _blocked_ptr(n_blocked), out.data_ptr(),
+                _stream_ptr())
+            native.check(st, "mpc_rollout_argmin_obstacles")
+            return out
         st = self.lib.mpc_rollout_argmin(
             ctypes.byref(problem), v_sc.data_ptr(), beta_sc.data_ptr(), n_cand, n_steps,
             int(index_base), float(incumbent), _integ(integrator),
@@ -83,10 +109,20 @@ class Expansion:
         native.check(st, "mpc_rollout_argmin")
         return out
 
-    def partials(self, problem: MpcProblem, v_sc, beta_sc, integrator="qk21"):
-        """Phase 1 only: the streaming rollout kernel (block arg-min records)."""
+    def partials(self, problem: MpcProblem, v_sc, beta_sc, integrator="qk21", obstacles=None,
+                 n_blocked=None):
+        """Phase 1 only: the streaming rollout kernel (block arg-min records).
+        obstacles / n_blocked: as in rollout_argmin (mpc_rollout_partials_obstacles)."""
         n_steps, n_cand = v_sc.shape
         ws = self._workspace(self.lib.mpc_workspace_bytes(n_cand, n_steps))
+        obs, n_obs = make_obstacles(obstacles)
+        if n_obs or n_blocked is not None:
+            st = self.lib.mpc_rollout_partials_obstacles(
+                ctypes.byref(problem), obs, n_obs, v_sc.data_ptr(), beta_sc.data_ptr(), n_cand,
+                n_steps, _integ(integrator), None, ws.data_ptr(), ws.numel(),
+                _blocked_ptr(n_blocked), _stream_ptr())
+            native.check(st, "mpc_rollout_partials_obstacles")
+            return
         st = self.lib.mpc_rollout_partials(ctypes.byref(problem), v_sc.data_ptr(),
                                            beta_sc.data_ptr(), n_cand, n_steps,
                                            _integ(integrator), None, ws.data_ptr(), ws.numel(),

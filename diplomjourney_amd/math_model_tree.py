@@ -58,6 +58,12 @@ prediction_horizon = 3
 # Radius of U-turn (:44)
 radius_u_turn = L / math.sin(beta_max)
 
+# Keep-out circles (x, y, r) in world coordinates: a candidate whose state
+# after any layer lies inside one never wins (mpc_rollout_argmin_obstacles).
+# The reference draws a "barrier_polygon" and reads it nowhere; this list is
+# what predictive_control scores against.  Empty: the reference's behaviour.
+barriers = []
+
 _engine = None
 
 
@@ -73,6 +79,17 @@ def engine():
         from .expansion import Expansion
         _engine = Expansion()
     return _engine
+
+
+def add_barrier_circle(x, y, r):
+    """Keep candidates out of the circle of radius r about (x, y).  r covers
+    the robot's size and the distance driven in one step: only layer states
+    are tested, not the path between them."""
+    barriers.append((float(x), float(y), float(r)))
+
+
+def clear_barriers():
+    del barriers[:]
 
 
 def reset_state():
@@ -93,6 +110,7 @@ def reset_state():
              result_trajectory_angle_speed=[0], actual_result_trajectory_angle_speed=[0],
              result_v=0, result_beta=0, m=0, steps_for_slowing=0,
              last_tree=None, last_result=None)
+    clear_barriers()
     for name in ("predicted_trajectory", "actual_predicted_trajectory"):
         for ax in ("x", "y", "phi"):
             for k in range(3):
@@ -307,8 +325,13 @@ def predictive_control(_initial_x, _initial_y, _initial_phi, _target_x, _target_
         v_sc, b_sc = candidate_controls(V, list(_vector_beta), prediction_horizon, eng.device)
         problem = make_problem(_initial_x, _initial_y, _initial_phi, x_t, y_t, x_0, y_0, L,
                                t, t + delta_t)
-        eng.rollout_argmin(problem, v_sc, b_sc, incumbent=optimal_criterion,
-                           integrator=INTEGRATOR, states=global_coordinates.states)
+        if barriers:
+            eng.rollout_argmin(problem, v_sc, b_sc, incumbent=optimal_criterion,
+                               integrator=INTEGRATOR, states=global_coordinates.states,
+                               obstacles=barriers)
+        else:
+            eng.rollout_argmin(problem, v_sc, b_sc, incumbent=optimal_criterion,
+                               integrator=INTEGRATOR, states=global_coordinates.states)
         global_coordinates.controls[0].copy_(v_sc[0])
         global_coordinates.controls[1].copy_(b_sc[0])
         res = eng.fetch()

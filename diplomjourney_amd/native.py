@@ -47,6 +47,7 @@ EXPORTS = (
     "mpc_fulltree_episodes_state_bytes", "mpc_fulltree_episodes_reset",
     "mpc_fulltree_episodes_run", "mpc_stream_probe_tiled", "mpc_sample_controls_tiled",
     "mpc_episode_run_workspace_bytes", "mpc_episode_run",
+    "mpc_rollout_partials_obstacles", "mpc_rollout_argmin_obstacles",
 )
 
 HIPCC_FLAGS = [
@@ -127,6 +128,13 @@ def lib():
     L.mpc_rollout_finalize.restype = ctypes.c_int
     L.mpc_rollout_finalize.argtypes = [ctypes.POINTER(MpcProblem), _P, _P, _I64, _I32, _I64, _D,
                                        _I32, _I32, _P, ctypes.c_size_t, _P, _P]
+    L.mpc_rollout_partials_obstacles.restype = ctypes.c_int
+    L.mpc_rollout_partials_obstacles.argtypes = [ctypes.POINTER(MpcProblem), _P, _I32, _P, _P, _I64,
+                                                 _I32, _I32, _P, _P, ctypes.c_size_t, _P, _P]
+    L.mpc_rollout_argmin_obstacles.restype = ctypes.c_int
+    L.mpc_rollout_argmin_obstacles.argtypes = [ctypes.POINTER(MpcProblem), _P, _I32, _P, _P, _I64,
+                                               _I32, _I64, _D, _I32, _P, _P, ctypes.c_size_t, _P,
+                                               _P, _P]
     L.mpc_batched_workspace_bytes.restype = ctypes.c_size_t
     L.mpc_batched_workspace_bytes.argtypes = [_I32, _I64, _I32]
     L.mpc_rollout_argmin_batched.restype = ctypes.c_int

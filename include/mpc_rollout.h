@@ -155,6 +155,51 @@ int mpc_rollout_finalize(const mpc_problem_t* p, const double* v_sc, const doubl
                          int32_t integrator, int32_t with_states, void* ws, size_t ws_bytes,
                          mpc_result_t* out, mpc_stream_t stream);
 
+/*
+ * Keep-out circles: the same expansion with candidates that drive into an
+ * obstacle excluded from the arg-min.
+ *   - An obstacle is a circle {x, y, r} in world coordinates; at most
+ *     MPC_MAX_OBSTACLES per call.
+ *   - A candidate is BLOCKED if for any step k = 1..n_steps and any circle its
+ *     state after step k satisfies (x_k - x)^2 + (y_k - y)^2 < r^2.  The start
+ *     pose is not tested (a robot that starts inside can leave), and only
+ *     step-end states are: the caller inflates r for the robot's size and for
+ *     the distance covered in one step.
+ *   - A blocked candidate never wins, whatever its cost.  If every candidate
+ *     is blocked the result is the "no finite cost" result: index -1, found 0.
+ *   - Ties and the incumbent test are those of mpc_rollout_argmin.  A NaN
+ *     state is not inside any circle (its NaN cost never wins anyway).
+ *   - n_obstacles == 0 launches the kernels of mpc_rollout_partials: the same
+ *     result byte for byte.
+ *   obstacles      host array of n_obstacles circles, read during the call only
+ *   n_blocked_out  optional device int64: the number of blocked candidates of
+ *                  this call (zeroed and written on `stream`); NULL skips it
+ * The other arguments, the workspace and the block records are those of
+ * mpc_rollout_partials / mpc_rollout_argmin, so mpc_rollout_finalize,
+ * mpc_select_winner and the multi-GPU exchange follow unchanged
+ * (mpc_rollout_argmin_obstacles = mpc_rollout_partials_obstacles +
+ * mpc_rollout_finalize).  MPC_ERR_ARG, before any HIP call: n_obstacles
+ * outside [0, MPC_MAX_OBSTACLES], obstacles NULL with n_obstacles > 0, a
+ * non-finite centre, r not finite or r <= 0.  The device-resident episode
+ * entries, the batched entry and the full tree take no obstacles.
+ */
+#define MPC_MAX_OBSTACLES 16
+typedef struct mpc_obstacle {
+  double x, y, r;
+} mpc_obstacle_t;
+
+int mpc_rollout_partials_obstacles(const mpc_problem_t* p, const mpc_obstacle_t* obstacles,
+                                   int32_t n_obstacles, const double* v_sc,
+                                   const double* beta_sc, int64_t n_cand, int32_t n_steps,
+                                   int32_t integrator, double* states_out, void* ws,
+                                   size_t ws_bytes, int64_t* n_blocked_out, mpc_stream_t stream);
+int mpc_rollout_argmin_obstacles(const mpc_problem_t* p, const mpc_obstacle_t* obstacles,
+                                 int32_t n_obstacles, const double* v_sc, const double* beta_sc,
+                                 int64_t n_cand, int32_t n_steps, int64_t index_base,
+                                 double incumbent, int32_t integrator, double* states_out,
+                                 void* ws, size_t ws_bytes, int64_t* n_blocked_out,
+                                 mpc_result_t* out, mpc_stream_t stream);
+
 /* Batched robots: R problems, robot r owns columns
  * [r*cand_per_problem, (r+1)*cand_per_problem) of the [n_steps][R*cand] SoA.
  * problems / incumbents (nullable => +inf) / out are device arrays of R.

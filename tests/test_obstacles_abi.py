@@ -1,0 +1,114 @@
+"""Keep-out circles, CPU side: the two exports, the mpc_obstacle_t layout, the
+argument checks (all before any HIP call) and the barrier list of
+math_model_tree.  No GPU."""
+import ctypes
+import math
+import os
+import re
+import subprocess
+
+import pytest
+
+from diplomjourney_amd import abi, native
+
+HEADER = native.HEADER
+NEW = ("mpc_rollout_partials_obstacles", "mpc_rollout_argmin_obstacles")
+
+
+@pytest.fixture(scope="module")
+def L():
+    if native.needs_build():
+        native.build()
+    return native.lib()
+
+
+def test_exports_declared_and_present(L):
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    for name in NEW:
+        assert name in native.EXPORTS
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert hasattr(L, name)
+
+
+def test_obstacle_layout_matches_c(tmp_path):
+    src = tmp_path / "layout_obs.c"
+    src.write_text(
+        '#include <stdio.h>\n#include <stddef.h>\n#include "mpc_rollout.h"\n'
+        "int main(void){printf(\"%zu %zu %zu %zu %d\\n\", sizeof(mpc_obstacle_t),"
+        " offsetof(mpc_obstacle_t, x), offsetof(mpc_obstacle_t, y), offsetof(mpc_obstacle_t, r),"
+        " MPC_MAX_OBSTACLES); return 0;}\n")
+    exe = tmp_path / "layout_obs"
+    subprocess.run(["gcc", "-I", os.path.dirname(HEADER), "-o", str(exe), str(src)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True,
+                                          check=True).stdout.split()]
+    O = abi.MpcObstacle
+    assert got == [24, 0, 8, 16, 16]
+    assert got == [ctypes.sizeof(O), O.x.offset, O.y.offset, O.r.offset, abi.MPC_MAX_OBSTACLES]
+
+
+def _circles(*xyr):
+    return (abi.MpcObstacle * len(xyr))(*[abi.MpcObstacle(*c) for c in xyr])
+
+
+def test_argument_validation_without_gpu(L):
+    """Every rejection happens before any HIP call (fake device pointers)."""
+    p = abi.make_problem(0, 0, 0.3, 2, 3, 0, 0, 0.5, 0.05, 0.1)
+    fake = ctypes.c_void_p(0x1000)
+    ok = _circles((1.0, 1.0, 0.5))
+    base = dict(p=ctypes.byref(p), obs=ok, n_obs=1, v=fake, b=fake, n=100, ns=3, base=0,
+                inc=1e300, integ=0, st=None, ws=fake, wsb=1 << 20, nb=None, out=fake)
+
+    def argmin(**kw):
+        a = {**base, **kw}
+        return L.mpc_rollout_argmin_obstacles(a["p"], a["obs"], a["n_obs"], a["v"], a["b"], a["n"],
+                                              a["ns"], a["base"], a["inc"], a["integ"], a["st"],
+                                              a["ws"], a["wsb"], a["nb"], a["out"], None)
+
+    def partials(**kw):
+        a = {**base, **kw}
+        return L.mpc_rollout_partials_obstacles(a["p"], a["obs"], a["n_obs"], a["v"], a["b"],
+                                                a["n"], a["ns"], a["integ"], a["st"], a["ws"],
+                                                a["wsb"], a["nb"], None)
+
+    many = _circles(*[(float(i), 0.0, 0.1) for i in range(abi.MPC_MAX_OBSTACLES + 1)])
+    for call in (argmin, partials):
+        assert call(n_obs=-1) == abi.MPC_ERR_ARG
+        assert call(obs=many, n_obs=abi.MPC_MAX_OBSTACLES + 1) == abi.MPC_ERR_ARG
+        assert call(obs=None, n_obs=1) == abi.MPC_ERR_ARG
+        for bad in ((math.nan, 0, 1), (0, math.inf, 1), (-math.inf, 0, 1), (0, 0, math.nan),
+                    (0, 0, math.inf), (0, 0, 0.0), (0, 0, -1.0)):
+            assert call(obs=_circles((1, 1, 1), bad), n_obs=2) == abi.MPC_ERR_ARG, bad
+        # the checks of the entries without obstacles hold as well
+        assert call(p=None) == abi.MPC_ERR_ARG
+        assert call(n=0) == abi.MPC_ERR_ARG
+        assert call(ns=abi.MPC_MAX_STEPS + 1) == abi.MPC_ERR_ARG
+        assert call(v=None) == abi.MPC_ERR_ARG
+        assert call(integ=7) == abi.MPC_ERR_UNSUPPORTED
+        assert call(integ=abi.MPC_INTEG_RECT | abi.MPC_LAYOUT_TILED) == abi.MPC_ERR_UNSUPPORTED
+        assert call(wsb=8) == abi.MPC_ERR_WORKSPACE
+    assert argmin(out=None) == abi.MPC_ERR_ARG
+    assert argmin(base=-1) == abi.MPC_ERR_ARG
+
+
+def test_make_obstacles():
+    assert abi.make_obstacles(None) == (None, 0) and abi.make_obstacles([]) == (None, 0)
+    arr, n = abi.make_obstacles([(1, 2, 3), (4.5, 5, 0.25)])
+    assert n == 2 and (arr[1].x, arr[1].y, arr[1].r) == (4.5, 5.0, 0.25)
+    with pytest.raises(ValueError):
+        abi.make_obstacles([(1, 2)])
+
+
+def test_barrier_list():
+    from diplomjourney_amd import math_model_tree as mmt
+    assert mmt.barriers == []
+    try:
+        mmt.add_barrier_circle(1, 2, 0.5)
+        mmt.add_barrier_circle(0.25, -1, 0.125)
+        assert mmt.barriers == [(1.0, 2.0, 0.5), (0.25, -1.0, 0.125)]
+        mmt.clear_barriers()
+        assert mmt.barriers == []
+        mmt.add_barrier_circle(1, 2, 0.5)
+        mmt.reset_state()
+        assert mmt.barriers == []
+    finally:
+        mmt.reset_state()
