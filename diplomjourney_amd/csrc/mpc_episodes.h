@@ -67,38 +67,11 @@ __global__ void k_episodes_reset(const mpc_episode_config_t* __restrict__ cfgs, 
   robots[r] = R;
 }
 
-// One candidate with constant control (v, b) over n_steps, exactly as the
-// rollout kernels evaluate it (rollout_candidate_l without the trajectory:
-// the core recurrence, and the safe one for an irregular candidate).
-template <int INTEG, int ROT, bool PL2>
-__device__ __forceinline__ double const_candidate_cost_l(const Consts& K, double v, double b,
-                                                         int n_steps) {
-  double x, y, ph, s, c;
-  step_start<ROT>(K, x, y, ph, s, c);
-  bool bad = false;
-  for (int st = 0; st < n_steps; ++st) step_core<INTEG, ROT, PL2>(x, y, ph, s, c, v, b, K, bad);
-  if constexpr (ROT == kRotCum) {
-    if (!bad) cum_pose<PL2>(K, x, y, x, y);
-  }
-  if (bad) {
-    x = K.x;
-    y = K.y;
-    ph = K.phi;
-    for (int st = 0; st < n_steps; ++st) step_safe<INTEG>(x, y, ph, v, b, K);
-  }
-  return cost(x, y, K);
-}
-
-template <int INTEG, int ROT>
-__device__ __forceinline__ double const_candidate_cost(const Consts& K, double v, double b,
-                                                       int n_steps) {
-  return K.L_pow2 ? const_candidate_cost_l<INTEG, ROT, true>(K, v, b, n_steps)
-                  : const_candidate_cost_l<INTEG, ROT, false>(K, v, b, n_steps);
-}
-
-// Two candidates' recurrences in one loop — independent chains the scheduler
-// interleaves — each with exactly const_candidate_cost_l's operations (the
-// same bits per candidate).
+// Two candidates with constant controls (v[j], b[j]) over n_steps, their
+// recurrences in one loop — independent chains the scheduler interleaves —
+// each exactly as the rollout kernels evaluate one candidate (rollout_candidate_l
+// without the trajectory: the core recurrence, step_core, and for an irregular
+// candidate the safe one, step_safe): the same bits per candidate.
 // NS > 0: the horizon as a compile-time constant (the reference's N = 3):
 // the loop unrolls, and the steps' sin/cos — which depend only on the heading
 // chain, a sum of the candidate's constant increment — overlap.
@@ -266,25 +239,21 @@ __device__ inline void wave_winner_states_l(const Consts& K, double v, double b,
     }
 }
 
-// Block r = robot r: up to max_calls MPC steps of its episode (fewer if it
-// ends).  log: [n][cap] ring per robot; progress (optional): {calls, stop,
-// candidates} per robot after the launch.
-// NT = 256: 4 waves per SIMD (<= 128 VGPRs), 4 robots per CU at a time; a
-// robot's serial phases (grid, re-roll, update: one lane) then share their
-// SIMD with three other robots' waves.
-// NT = 64 (the default for N <= 21): ONE wave per robot — 1000 robots are
-// ~1 wave per SIMD, so the serial phases run uncontended; a lane rolls out
-// its candidates two at a time (const_pair_cost), the arg-min is one DPP
-// wave reduction and the barriers are a single wave's.
-// PAIR: a lane's candidates two at a time, interleaved (const_pair_cost);
-// else one after the other (more waves per SIMD fit: <= 128 VGPRs).
-constexpr int kEpisodesWaves = 4;
-template <int INTEG, int ROT, int NT = kBlock, bool PAIR = (NT == 64)>
-__global__ __launch_bounds__(NT, PAIR ? 2 : kEpisodesWaves) void k_episodes_run(
+// Block r = robot r (kBlock threads): up to max_calls MPC steps of its episode
+// (fewer if it ends).  log: [n][cap] ring per robot; progress (optional):
+// {calls, stop, candidates} per robot after the launch.
+// Lane l rolls out candidates l, l + kBlock, ... two at a time, interleaved
+// (const_pair_cost): two independent chains per lane cover the recurrence's
+// latency, at the price of registers: the launch bound asks for 2 waves per
+// SIMD (<= 256 VGPRs), so 2 robots per CU at a time.  A robot's serial phases
+// (grid, re-roll, update: one wave or one lane) share their SIMD with the
+// other resident robot's waves.  (One candidate at a time, and one wave per
+// robot, were measured and not kept: DESIGN.md §1 and §6f.)
+template <int INTEG, int ROT>
+__global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
     const mpc_episode_config_t* __restrict__ cfgs, RobotState* __restrict__ robots, int n_steps,
     int max_calls, mpc_episode_log_t* __restrict__ log, int cap,
     mpc_episodes_progress_t* __restrict__ progress) {
-  static_assert(NT == 64 || NT == kBlock, "one wave or one standard block per robot");
   const int r = blockIdx.x;
   const mpc_episode_config_t& c = cfgs[r];
   RobotState* __restrict__ R = &robots[r];
@@ -296,7 +265,7 @@ __global__ __launch_bounds__(NT, PAIR ? 2 : kEpisodesWaves) void k_episodes_run(
   __shared__ mpc_episode_log_t s_log;
   __shared__ mpc_result_t s_out;
   __shared__ EmitLds lds;
-  for (int q = threadIdx.x; q < kStoredWords; q += NT)
+  for (int q = threadIdx.x; q < kStoredWords; q += kBlock)
     s_head[q] = reinterpret_cast<const uint64_t*>(R)[q];
   if (threadIdx.x == 0) {
     s_stop = R->stop;
@@ -321,51 +290,31 @@ __global__ __launch_bounds__(NT, PAIR ? 2 : kEpisodesWaves) void k_episodes_run(
     const int nv = s_nv, nb = s_nb, n_grid = nv * nb;
     uint64_t best_k = ~0ull;
     int64_t best_i = INT64_MAX;
-    if constexpr (PAIR) {
-      // lane l: candidates l, l + NT, l + 2 NT, ... two per pass (ascending per
-      // lane: strict < keeps the first)
-      for (int k0 = threadIdx.x; k0 < n_grid; k0 += 2 * NT) {
-        const int k1 = k0 + NT;
-        const bool has1 = k1 < n_grid;
-        const int kq = has1 ? k1 : k0;   // (a valid stand-in; its cost is not used)
-        const double vv[2] = {s_v[k0 / nb], s_v[kq / nb]};
-        const double bb[2] = {s_b[k0 % nb], s_b[kq % nb]};
-        double cst[2];
-        if (n_steps == 3)   // uniform: the reference's horizon, unrolled
-          const_pair_cost<INTEG, ROT, 3>(K, vv, bb, n_steps, cst);
-        else
-          const_pair_cost<INTEG, ROT>(K, vv, bb, n_steps, cst);
-        uint64_t kk = cost_key_nonneg(cst[0]);
-        if (kk < best_k) {
-          best_k = kk;
-          best_i = k0;
-        }
-        kk = cost_key_nonneg(cst[1]);
-        if (has1 && kk < best_k) {
-          best_k = kk;
-          best_i = k1;
-        }
+    // lane l: candidates l, l + kBlock, l + 2 kBlock, ... two per pass (ascending
+    // per lane: strict < keeps the first)
+    for (int k0 = threadIdx.x; k0 < n_grid; k0 += 2 * kBlock) {
+      const int k1 = k0 + kBlock;
+      const bool has1 = k1 < n_grid;
+      const int kq = has1 ? k1 : k0;   // (a valid stand-in; its cost is not used)
+      const double vv[2] = {s_v[k0 / nb], s_v[kq / nb]};
+      const double bb[2] = {s_b[k0 % nb], s_b[kq % nb]};
+      double cst[2];
+      if (n_steps == 3)   // uniform: the reference's horizon, unrolled
+        const_pair_cost<INTEG, ROT, 3>(K, vv, bb, n_steps, cst);
+      else
+        const_pair_cost<INTEG, ROT>(K, vv, bb, n_steps, cst);
+      uint64_t kk = cost_key_nonneg(cst[0]);
+      if (kk < best_k) {
+        best_k = kk;
+        best_i = k0;
       }
-    } else {
-      for (int k0 = 2 * threadIdx.x; k0 < n_grid; k0 += 2 * kBlock) {
-#pragma unroll 1
-        for (int j = 0; j < 2; ++j) {
-          const int k = k0 + j;   // ascending per lane: strict < keeps the first
-          if (k < n_grid) {
-            const uint64_t kk = cost_key_nonneg(
-                const_candidate_cost<INTEG, ROT>(K, s_v[k / nb], s_b[k % nb], n_steps));
-            if (kk < best_k) {
-              best_k = kk;
-              best_i = k;
-            }
-          }
-        }
+      kk = cost_key_nonneg(cst[1]);
+      if (has1 && kk < best_k) {
+        best_k = kk;
+        best_i = k1;
       }
     }
-    if constexpr (NT == 64)
-      wave_argmin32(best_k, best_i);   // (every lane holds the minimum)
-    else
-      block_argmin<true>(best_k, best_i);
+    block_argmin<true>(best_k, best_i);
     if (threadIdx.x == 0) {
       s_bk = best_k;
       s_bi = best_i;
@@ -435,7 +384,8 @@ __global__ __launch_bounds__(NT, PAIR ? 2 : kEpisodesWaves) void k_episodes_run(
           [threadIdx.x] = reinterpret_cast<const uint64_t*>(&s_log)[threadIdx.x];
   }
   __syncthreads();
-  for (int q = threadIdx.x; q < kStoredWords; q += NT) reinterpret_cast<uint64_t*>(R)[q] = s_head[q];
+  for (int q = threadIdx.x; q < kStoredWords; q += kBlock)
+    reinterpret_cast<uint64_t*>(R)[q] = s_head[q];
   if (threadIdx.x == 0) {
     R->stop = s_stop;
     R->calls = s_calls;

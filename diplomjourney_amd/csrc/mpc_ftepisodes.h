@@ -1,27 +1,39 @@
 // mpc_ftepisodes.h — run_math_model.py's episode loop (:231-280) over its own
 // FULL-TREE MPC step (:133-228), R episodes device-resident.
 //
-// Two forms.  The default (mpc_fulltree_episodes_run) is the load-balanced
-// lockstep form at the end of this file: per call, the leaves of every robot
-// still running spread over the whole GPU.  k_ft_episodes_run (build with
-// -DMPC_FT_LOCKSTEP=0) is the round-5 form, kept as its A/B reference:
-// one block per robot runs its episode's MPC steps back to back in ONE launch
-// (the structure of mpc_episodes.h, with the full tree as the step):
+// Load-balanced lockstep: every call of mpc_fulltree_episodes_run is three
+// launches over the robots still running, the leaves of each spread over the
+// whole GPU.  (One block per robot running its whole episode in one launch
+// left a robot's CU idle once its episode had stopped: at workload G, 1000
+// episodes of 50 calls, 40 % of the robot-calls, 30,257 of 50,000, were idle,
+// and the last calls ran a few long episodes on a few CUs.)
 //
-//   per MPC step of robot r (block r):
+//   per MPC step (call) of the robots still running:
+//   k_ftl_prepare  one block
 //     stop rules    on target (:261) / the caller's call limit, checked before
-//                   the step as the script's `while` and run_batched do
-//     window        t += delta_t (:156); the step's constants from the pose,
-//                   the episode's target and line origin (consts_from_problem)
+//                   the step as the script's `while` and run_batched do; the
+//                   live robots compacted in ascending order
+//     window        t += delta_t (:156); each live robot's step constants from
+//                   its pose, the episode's target and line origin
+//                   (consts_from_problem) into FtRobot
 //     controls      the S1 = |V|*|B| per-control factors (FtCtl: v*h, dphi of
-//                   the quad window, rotation factors) into LDS, one thread per
-//                   control; a step with some |dphi| > kRotMax runs the direct
-//                   sin/cos form (as k_ft_controls' launch-wide flag)
-//     leaves        the S1^3 leaves (:158-197) as k_ft_leaves scores them
-//                   (ft_leaves_body: lane = (k0, k1) pair, k2 wave-uniform),
-//                   spread over the block's 4 waves; lexicographic (cost, j)
-//                   block minimum; found = cost < the robot's never-reset
-//                   optimal_criterion (:193-196)
+//                   the quad window, rotation factors), one thread per control
+//                   (k_ft_controls' arithmetic) — ONE table for all robots:
+//                   every live robot has run the same number of calls, so its
+//                   window [t, t + dt] is the same sum of the same dt's; a step
+//                   with some |dphi| > kRotMax runs the direct sin/cos form
+//                   (FtLockstep::no_rot, as k_ft_controls' launch-wide flag)
+//   k_ftl_leaves   a fixed grid spread over the live robots: bpr = grid / n_live
+//                  blocks per robot
+//     leaves        a robot's S1^3 leaves (:158-197) as k_ft_leaves scores them
+//                   (ft_leaves_body: lane = (k0, k1) pair, k2 wave-uniform, the
+//                   control table read as wave-uniform scalar loads), in
+//                   bpr x 4 equal contiguous wave shares; one lexicographic
+//                   (cost, leaf) record per block — the minimum does not depend
+//                   on how the leaves were split
+//   k_ftl_update   one block per live robot
+//     arg-min       its bpr records -> the first strict minimum; found = cost <
+//                   the robot's never-reset optimal_criterion (:193-196)
 //     update        a winner's first layer (re-derived with ft_apply) + its
 //                   control becomes optimal_trajectory[0][0]; without a winner
 //                   the stale one is returned again (the script re-reads it);
@@ -49,12 +61,9 @@ struct FtEpisode {
   int64_t leaves;                  // leaves scored so far
 };
 
-// Largest S1 whose control table (48 B per control) fits the LDS: 24 KiB per
-// block, so the LDS never limits the 4 blocks per CU below.
+// Largest S1 the entry accepts: the scratch holds one control table of this
+// many controls (48 B each, 24 KiB: ftl_live_offset).
 constexpr int kFtEpMaxS1 = 512;
-// 4 waves per SIMD: 4 robots per CU at a time (1024 resident blocks), <= 128
-// VGPRs for the leaf loop (both heading forms instantiated).
-constexpr int kFtEpWaves = 4;
 
 __global__ void k_ft_episodes_reset(const mpc_fulltree_episode_config_t* __restrict__ cfgs,
                                     int n, FtEpisode* __restrict__ eps) {
@@ -77,176 +86,7 @@ __global__ void k_ft_episodes_reset(const mpc_fulltree_episode_config_t* __restr
   eps[r] = E;
 }
 
-// Block r = robot r: up to max_calls MPC steps of its episode (fewer if it
-// stops).  log: [n][cap] ring per robot; progress: {calls, stop, leaves}.
-template <int INTEG, bool ROT>
-__global__ __launch_bounds__(kBlock, kFtEpWaves) void k_ft_episodes_run(
-    FtEpisode* __restrict__ eps, const double* __restrict__ V, int nv,
-    const double* __restrict__ B, int nb, double L, double delta_t, double eps_target,
-    int max_calls, mpc_episode_log_t* __restrict__ log, int cap,
-    mpc_episodes_progress_t* __restrict__ progress) {
-  const int r = blockIdx.x;
-  __shared__ __attribute__((aligned(16))) FtCtl s_ctl[kFtEpMaxS1];
-  __shared__ FtEpisode s_e;
-  __shared__ mpc_episode_log_t s_log;
-  __shared__ int s_run;
-  if (threadIdx.x == 0) s_e = eps[r];
-  const int64_t s1 = static_cast<int64_t>(nv) * nb;
-  const int64_t n_items = ft_units(s1);
-  const int64_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int call = 0; call < max_calls; ++call) {
-    if (threadIdx.x == 0) {   // the loop's head (:261) and the caller's limit
-      if (s_e.stop == 0) {
-        const double ex = s_e.x_t - s_e.x, ey = s_e.y_t - s_e.y;
-        if (ex * ex + ey * ey <= eps_target)
-          s_e.stop = MPC_EP_ARRIVED;
-        else if (s_e.max_calls > 0 && s_e.calls >= s_e.max_calls)
-          s_e.stop = MPC_EP_LIMIT;
-      }
-      s_run = s_e.stop == 0;
-    }
-    __syncthreads();
-    if (!s_run) break;   // uniform
-    const double t_a = s_e.t + delta_t;                        // t += delta_t (:156)
-    mpc_problem_t q;
-    q.x = s_e.x;
-    q.y = s_e.y;
-    q.phi = s_e.phi;
-    q.x_t = s_e.x_t;
-    q.y_t = s_e.y_t;
-    q.x_0 = s_e.x_0;
-    q.y_0 = s_e.y_0;
-    q.L = L;
-    q.t_a = t_a;
-    q.t_b = t_a + delta_t;
-    const Consts K = uniform_consts(consts_from_problem(q));
-    const double atan_t = s_e.atan_t;
-    // the step's control table (k_ft_controls' arithmetic), in LDS
-    bool wide = false;
-    for (int64_t k = threadIdx.x; k < s1; k += kBlock) {
-      FtCtl u;
-      u.v = V[k / nb];
-      u.beta = B[k % nb];
-      u.vh = u.v * K.h;
-      const double w = K.L_pow2 ? u.v * K.inv_L : u.v / K.L;
-      u.dphi = heading_incr<INTEG>(w, trig::tan_fast(u.beta), K);
-      if (fabs(u.dphi) <= trig::kRotMax) {
-        trig::rotation_sc(u.dphi, u.sd, u.cd);
-      } else {
-        u.sd = u.cd = 0.0;
-        wide = true;
-      }
-      s_ctl[k] = u;
-    }
-    // (the barrier that publishes the table: evaluated in every instantiation,
-    // not short-circuited away by a false ROT)
-    const bool any_wide = __syncthreads_or(wide);
-    const bool rot = ROT && !any_wide;
-    uint64_t best_k = ~0ull;
-    int64_t best_i = INT64_MAX;
-    const FtCrit F = ft_crit(K, atan_t);
-    if (rot)
-      ft_leaves_body<INTEG, true>(K, F, s_ctl, s1, 0, n_items, best_k, best_i, wave, kWaves);
-    else
-      ft_leaves_body<INTEG, false>(K, F, s_ctl, s1, 0, n_items, best_k, best_i, wave, kWaves);
-    block_argmin(best_k, best_i);
-    if (threadIdx.x == 0) {   // the update of run_batched (run_math_model.py)
-      FtEpisode& E = s_e;
-      mpc_episode_log_t& Lg = s_log;
-      const double c = key_cost(best_k);
-      const bool found = best_k != ~0ull && c < E.crit;
-      int32_t status = 0;
-      E.t = t_a;
-      if (found) {
-        E.crit = c;
-        const int64_t k0 = best_i / (s1 * s1);
-        const FtCtl u = s_ctl[k0];
-        const FtState s0{K.x, K.y, K.phi, K.s0, K.c0};
-        const FtState l0 = rot ? ft_apply<INTEG, true>(s0, u, K) : ft_apply<INTEG, false>(s0, u, K);
-        E.stale[0] = l0.x;
-        E.stale[1] = l0.y;
-        E.stale[2] = l0.ph;
-        E.stale[3] = u.v;
-        E.stale[4] = u.beta;
-        E.has_stale = 1;
-      } else {
-        status |= MPC_EP_STALE;
-      }
-      if (!E.has_stale) {
-        // optimal_trajectory is still the script's [0]: its first call raises
-        // TypeError ('int' object is not subscriptable) — the episode stops
-        status |= MPC_EP_NO_TRAJ;
-        E.stop = status;
-      } else {
-        E.x = E.stale[0];
-        E.y = E.stale[1];
-        E.phi = E.stale[2];
-        E.v = E.stale[3];
-        E.beta = E.stale[4];
-        if (E.x == E.prev_x && E.y == E.prev_y) {   // :266-270
-          E.k += 1;
-          status |= MPC_EP_STUCK;
-        }
-        if (E.k == 2) {
-          status |= MPC_EP_BREAK;
-          E.stop = status;
-        }
-        E.prev_x = E.x;
-        E.prev_y = E.y;
-      }
-      Lg.step = E.calls;
-      Lg.index = found ? best_i : -1;
-      Lg.p = E.calls + 1;
-      Lg.episode = 1;
-      Lg.found = found ? 1 : 0;
-      Lg.status = status;
-      Lg.cost = E.crit;
-      Lg.x = E.x;
-      Lg.y = E.y;
-      Lg.phi = E.phi;
-      Lg.v = E.v;
-      Lg.beta = E.beta;
-      E.calls += 1;
-      E.leaves += s1 * s1 * s1;
-    }
-    __syncthreads();
-    if (log && cap > 0 && threadIdx.x < kLogWords)
-      reinterpret_cast<uint64_t*>(&log[static_cast<int64_t>(r) * cap + s_log.step % cap])
-          [threadIdx.x] = reinterpret_cast<const uint64_t*>(&s_log)[threadIdx.x];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    eps[r] = s_e;
-    if (progress) {
-      progress[r].calls = s_e.calls;
-      progress[r].stop = s_e.stop;
-      progress[r].candidates = s_e.leaves;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Load-balanced lockstep form of the same episodes (the default of
-// mpc_fulltree_episodes_run).  One block per robot leaves a robot's CU idle
-// once its episode has stopped: at workload G (1000 episodes, 50 calls) 40 %
-// of the lockstep slots were idle (30,257 robot-calls of 50,000), and the
-// last calls ran a few long episodes on a few CUs.  Here every call is three
-// launches over the robots still running:
-//   k_ftl_prepare  one block: the stop rules of every robot (the loop head,
-//                  :261, and the call limit), the live robots compacted in
-//                  ascending order, their step constants (FtRobot), and the
-//                  call's control table — ONE table for all of them: every
-//                  live robot has run the same number of calls, so its window
-//                  [t, t + dt] is the same sum of the same dt's
-//   k_ftl_leaves   a fixed grid spread over the live robots: bpr = grid /
-//                  n_live blocks per robot (its S1^3 leaves in bpr x 4
-//                  equal contiguous wave shares, ft_leaves_body, the control
-//                  table read as wave-uniform scalar loads as in k_ft_leaves)
-//   k_ftl_update   one block per live robot: its bpr records -> the first
-//                  strict minimum, then exactly k_ft_episodes_run's update.
-// The leaves' costs are the per-robot kernel's (same table, same constants,
-// same ft_leaf); the lexicographic (cost, leaf) minimum does not depend on
-// how the leaves were split, so the two forms log the same bits.
+// The call's launch-wide facts, written by k_ftl_prepare.
 struct FtLockstep {
   int32_t n_live, bpr, no_rot, pad_;
 };
@@ -413,7 +253,7 @@ __global__ __launch_bounds__(kBlock) void k_ftl_update(
     }
   }
   block_argmin(best_k, best_i);
-  if (threadIdx.x == 0) {   // k_ft_episodes_run's update (run_batched, run_math_model.py)
+  if (threadIdx.x == 0) {   // the update of run_batched (run_math_model.py)
     FtEpisode E = eps[r];
     const Consts& K = robots[r].K;
     const bool rot = ROT && ls->no_rot == 0;
@@ -438,6 +278,8 @@ __global__ __launch_bounds__(kBlock) void k_ftl_update(
       status |= MPC_EP_STALE;
     }
     if (!E.has_stale) {
+      // optimal_trajectory is still the script's [0]: its first call raises
+      // TypeError ('int' object is not subscriptable) — the episode stops
       status |= MPC_EP_NO_TRAJ;
       E.stop = status;
     } else {

@@ -34,6 +34,13 @@ double (*volatile g_libm_pow)(double, double) = pow;
 double (*volatile g_libm_sin)(double) = sin;
 double (*volatile g_libm_cos)(double) = cos;
 
+// The wheelbase is a power of two: sums scaled by 1/L are then exact, which the
+// PL2 kernel instantiations and Consts::L_pow2 (consts_from_problem) rely on.
+inline bool length_pow2(double L) {
+  int e;
+  return frexp(L, &e) == 0.5;
+}
+
 // Problem constants derived on the host with the reference's libm calls.
 Consts host_consts(const mpc_problem_t& p) {
   Consts K;
@@ -51,8 +58,7 @@ Consts host_consts(const mpc_problem_t& p) {
   K.C2 = p.y_t * p.x_0;
   K.inv_den = 1.0 / sqrt(g_libm_pow(K.A, 2.0) + g_libm_pow(K.B, 2.0));
   K.L = p.L;
-  int e;
-  K.L_pow2 = (frexp(p.L, &e) == 0.5) ? 1 : 0;
+  K.L_pow2 = length_pow2(p.L) ? 1 : 0;
   K.inv_L = K.L_pow2 ? 1.0 / p.L : 0.0;
   K.h = p.t_b - p.t_a;
   K.hlgth = 0.5 * (p.t_b - p.t_a);
@@ -122,95 +128,119 @@ bool chain_ctl_ok(const double* v, const double* b, int64_t n_cand, int32_t inte
   return is_tiled(integrator) ? tiled_ok(v, b, n_cand) : wide_ok(v, b, n_cand);
 }
 
+// Facts about the current device, each cached per device on first use.
+constexpr int kMaxDevices = 16;
+
+// The current device's slot in those caches; not `known` (slot 0) when there is
+// no device or its index is past them.
+struct DeviceSlot {
+  int dev;
+  bool known;
+};
+DeviceSlot device_slot() {
+  int dev = 0;
+  const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices;
+  return {known ? dev : 0, known};
+}
+
+// Its CU count (256 when the query fails).
+int64_t device_cus() {
+  static int64_t cache[kMaxDevices] = {0};
+  const int dev = device_slot().dev;
+  if (cache[dev] == 0) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus < 1)
+      cus = 256;
+    cache[dev] = cus;
+  }
+  return cache[dev];
+}
+
 // The bounded device waits count wall_clock64 ticks at kWallHz
 // (mpc_episode.h).  A device whose constant-rate clock runs at another rate
 // would scale every budget silently: the entries with such waits refuse it.
 // Unknown (no device / the query fails): not refused here (the launch reports).
 bool wall_clock_ok() {
-  static int cache[16] = {0};   // 0 unknown, 1 kWallHz, -1 another rate
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return true;
-  if (cache[dev] == 0) {
+  static int cache[kMaxDevices] = {0};   // 0 unknown, 1 kWallHz, -1 another rate
+  const DeviceSlot d = device_slot();
+  if (!d.known) return true;
+  if (cache[d.dev] == 0) {
     int khz = 0;
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess ||
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, d.dev) != hipSuccess ||
         khz <= 0)
       return true;
-    cache[dev] = static_cast<uint64_t>(khz) * 1000ull == kWallHz ? 1 : -1;
+    cache[d.dev] = static_cast<uint64_t>(khz) * 1000ull == kWallHz ? 1 : -1;
   }
-  return cache[dev] == 1;
+  return cache[d.dev] == 1;
 }
 
+// Blocks of kBlock threads of one kernel instantiation that the device holds at
+// once (occupancy x CUs).
+template <auto Kernel>
+int64_t resident_blocks() {
+  static int64_t cache[kMaxDevices] = {0};
+  const int dev = device_slot().dev;
+  if (cache[dev] == 0) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu, reinterpret_cast<const void*>(Kernel), kBlock, 0) != hipSuccess ||
+        per_cu < 1)
+      per_cu = 1;
+    cache[dev] = per_cu * device_cus();
+  }
+  return cache[dev];
+}
+
+// Runtime bools -> f(BC<b0>{}, BC<b1>{}, ...): one call per combination, so a
+// kernel's bool template parameters can follow runtime decisions.
+template <class F, class... Bs>
+void dispatch_bools(F&& f, bool b, Bs... rest) {
+  if constexpr (sizeof...(rest) == 0) {
+    b ? f(BC<true>{}) : f(BC<false>{});
+  } else {
+    b ? dispatch_bools([&](auto... t) { f(BC<true>{}, t...); }, rest...)
+      : dispatch_bools([&](auto... t) { f(BC<false>{}, t...); }, rest...);
+  }
+}
+
+// integrator -> f(IC<INTEG>, BC<ROT>): the integrator and whether the heading is
+// a rotation.  As it stands, the full-tree kernels' dispatch (direct or rotation
+// heading only: their entries refuse MPC_HEADING_CUMULATIVE).  The tags convert
+// to their values, so a lambda's (auto I, auto R) go straight into k<I, R>.
+template <class F>
+void dispatch_integ_rot(int32_t integrator, F&& f) {
+  dispatch_bools(
+      [&](auto rect, auto rot) { f(IC<rect ? MPC_INTEG_RECT : MPC_INTEG_QK21>{}, rot); },
+      (integrator & 0xff) == MPC_INTEG_RECT, (integrator & MPC_HEADING_ROTATE) != 0);
+}
+
+// integrator -> f(IC<INTEG>, IC<ROT>), ROT as described above mode_ok.
 template <class F>
 void dispatch_mode(int32_t integrator, F&& f) {
-  const bool rot = (integrator & MPC_HEADING_ROTATE) != 0;
-  if ((integrator & 0xff) == MPC_INTEG_RECT) {
-    if (is_cum(integrator)) f(IC<MPC_INTEG_RECT>{}, IC<kRotCum>{});
-    else if (rot) f(IC<MPC_INTEG_RECT>{}, IC<1>{});
-    else f(IC<MPC_INTEG_RECT>{}, IC<0>{});
-  } else {
-    if (rot) f(IC<MPC_INTEG_QK21>{}, IC<1>{});
-    else f(IC<MPC_INTEG_QK21>{}, IC<0>{});
-  }
+  if ((integrator & 0xff) == MPC_INTEG_RECT && is_cum(integrator))
+    f(IC<MPC_INTEG_RECT>{}, IC<kRotCum>{});
+  else
+    dispatch_integ_rot(integrator, [&](auto integ, auto rot) { f(integ, IC<rot ? 1 : 0>{}); });
 }
 
-// The full-tree kernels: direct or rotation heading only.
-template <class F>
-void dispatch_mode2(int32_t integrator, F&& f) {
-  const bool rot = (integrator & MPC_HEADING_ROTATE) != 0;
-  if ((integrator & 0xff) == MPC_INTEG_RECT) {
-    if (rot) f(IC<MPC_INTEG_RECT>{}, BC<true>{});
-    else f(IC<MPC_INTEG_RECT>{}, BC<false>{});
-  } else {
-    if (rot) f(IC<MPC_INTEG_QK21>{}, BC<true>{});
-    else f(IC<MPC_INTEG_QK21>{}, BC<false>{});
-  }
-}
-
-// Resident blocks of one fused episode instantiation (occupancy x CUs), cached
-// per instantiation and device.  The fused launch is sized to ONE resident
-// round: each block's end-of-launch hand-off (sc1 store + counter atomic) is
-// then paid once per block, not once per tile round.
+// The fused episode launch is sized to ONE resident round of its instantiation:
+// each block's end-of-launch hand-off (sc1 store + counter atomic) is then paid
+// once per block, not once per tile round.
 template <int CPL, int I, int R>
 int64_t fused_grid(int64_t n_cand) {
-  static int64_t cache[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  if (cache[dev] == 0) {
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, reinterpret_cast<const void*>(&k_rollout_episode<CPL, I, R>), kBlock, 0) !=
-            hipSuccess ||
-        per_cu < 1)
-      per_cu = 1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus < 1)
-      cus = 256;
-    cache[dev] = std::min<int64_t>(static_cast<int64_t>(per_cu) * cus, kMaxBlocks);
-  }
-  return std::max<int64_t>(1, std::min(cdiv(n_cand, kBlock * CPL), cache[dev]));
+  const int64_t resident =
+      std::min<int64_t>(resident_blocks<&k_rollout_episode<CPL, I, R>>(), kMaxBlocks);
+  return std::max<int64_t>(1, std::min(cdiv(n_cand, kBlock * CPL), resident));
 }
 
-// Tile blocks of one run launch: one resident round of the instantiation
-// (occupancy x CUs; more would only queue behind it), at most one per unit.
+// Tile blocks of one run launch: one resident round of the instantiation (more
+// would only queue behind it) less block 0, the selector, which takes one of
+// the slots; at most one per unit.
 template <bool P, bool T>
 int64_t run_tile_blocks(int64_t units) {
-  static int64_t cache[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  if (cache[dev] == 0) {
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, reinterpret_cast<const void*>(&k_episode_run<P, T>), kBlock, 0) !=
-            hipSuccess ||
-        per_cu < 1)
-      per_cu = 1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus < 1)
-      cus = 256;
-    // block 0 (the selector) takes one of the slots
-    cache[dev] = std::max<int64_t>(1, static_cast<int64_t>(per_cu) * cus - 1);
-  }
-  return std::max<int64_t>(1, std::min(units, cache[dev]));
+  const int64_t resident = std::max<int64_t>(1, resident_blocks<&k_episode_run<P, T>>() - 1);
+  return std::max<int64_t>(1, std::min(units, resident));
 }
 
 // Number of block records the rollout launch for these arguments writes
@@ -226,9 +256,7 @@ template <bool KDEV>
 void launch_rollout(hipStream_t st, int32_t integrator, const Consts& K, const Consts* Kdev,
                     const double* v, const double* b, int64_t n_cand, int n_steps, Rec* part) {
   const bool wide = wide_ok(v, b, n_cand);
-  dispatch_mode(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr int R = decltype(rot)::value;
+  dispatch_mode(integrator, [&](auto I, auto R) {
     if (wide)
       k_rollout_argmin_stream<I, R, KDEV><<<rollout_grid<kCplWide>(n_cand), kBlock, 0, st>>>(
           K, Kdev, v, b, n_cand, n_steps, part);
@@ -277,9 +305,7 @@ void launch_rollout_obs(hipStream_t st, int32_t integrator, const Consts& K, con
                         int n_obs, const double* v, const double* b, int64_t n_cand, int n_steps,
                         Rec* part, double* states, unsigned long long* n_blocked) {
   const bool wide = !states && wide_ok(v, b, n_cand);
-  dispatch_mode(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr int R = decltype(rot)::value;
+  dispatch_mode(integrator, [&](auto I, auto R) {
     constexpr int kAll = MPC_MAX_OBSTACLES;
     const dim3 g1(static_cast<unsigned>(rollout_grid<1>(n_cand)));
     const dim3 g2(static_cast<unsigned>(rollout_grid<kCplWide>(n_cand)));
@@ -307,9 +333,7 @@ void launch_finalize(hipStream_t st, int32_t integrator, const Rec* part, int n_
                      int64_t n_cand, int n_steps, int64_t index_base, double incumbent,
                      const double* incumbent_dev, mpc_result_t* out,
                      const mpc_episode_config_t& ecfg, const EpisodeHook& hook) {
-  dispatch_mode(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr int R = decltype(rot)::value;
+  dispatch_mode(integrator, [&](auto I, auto R) {
     if constexpr (KDEV && R == kRotCum) {
       if (is_tiled(integrator)) {   // the flush of a tiled chained episode
         k_finalize<I, R, KDEV, true><<<1, kFinBlock, 0, st>>>(
@@ -331,6 +355,63 @@ int check_episode_cfg(const mpc_episode_config_t* c) {
       (c->stop_rule != 0 && c->stop_rule != 1))
     return MPC_ERR_ARG;
   return MPC_OK;
+}
+
+int check_episode_arrays(const void* state, const void* v_sc, const void* beta_sc, int64_t n_cand,
+                         int32_t n_steps) {
+  if (!state || !v_sc || !beta_sc || n_cand < 1 || n_steps < 1 || n_steps > MPC_MAX_STEPS)
+    return MPC_ERR_ARG;
+  return MPC_OK;
+}
+
+bool workspace_ok(const void* ws, size_t ws_bytes, int64_t n_cand, int32_t n_steps) {
+  return ws && ws_bytes >= mpc_workspace_bytes(n_cand, n_steps);
+}
+
+// The chained-episode entries validate in one order, which is the precedence of
+// their statuses: arguments (MPC_ERR_ARG), then mode and control layout
+// (MPC_ERR_UNSUPPORTED), then the workspace (MPC_ERR_WORKSPACE), then what an
+// entry checks late, and the device's wall clock last (wall_clock_ok: the only
+// check that asks the runtime).  Each entry adds its own conditions to a stage.
+
+// The arguments every such entry takes (its controls: arrays, or arrays of rows).
+bool chained_args_ok(const mpc_episode_config_t* cfg, const void* state, const void* v,
+                     const void* b, int64_t n_cand, int32_t n_steps, int64_t index_base,
+                     int32_t log_capacity, uint32_t epoch) {
+  return check_episode_cfg(cfg) == MPC_OK &&
+         check_episode_arrays(state, v, b, n_cand, n_steps) == MPC_OK && index_base >= 0 &&
+         log_capacity >= 0 && epoch != 0;
+}
+
+// The chained kernels' one mode: rect + cumulative heading.
+bool chained_mode_ok(int32_t integrator, bool allow_tiled) {
+  return mode_ok(integrator, true, allow_tiled) == MPC_OK && is_cum(integrator);
+}
+
+// mpc_episode_finalize / mpc_episode_rollout: the same checks in the same
+// order; only the former accepts tiled controls (the flush of a tiled chained
+// episode, which needs the episode update).
+int check_episode_finish(const void* state, const double* v_sc, const double* beta_sc,
+                         int64_t n_cand, int32_t n_steps, int64_t index_base, int32_t integrator,
+                         bool allow_tiled, const void* ws, size_t ws_bytes, const mpc_result_t* out,
+                         const mpc_episode_config_t* advance, int32_t log_capacity) {
+  if (check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK || !out ||
+      index_base < 0)
+    return MPC_ERR_ARG;
+  if (mode_ok(integrator, true, allow_tiled) != MPC_OK) return MPC_ERR_UNSUPPORTED;
+  if (is_tiled(integrator) && (!is_cum(integrator) || !advance || !tiled_ok(v_sc, beta_sc, n_cand)))
+    return MPC_ERR_UNSUPPORTED;
+  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
+  if (advance && (check_episode_cfg(advance) != MPC_OK || log_capacity < 0)) return MPC_ERR_ARG;
+  return MPC_OK;
+}
+
+// The finalize kernels' episode update: the state to advance, the log and the
+// words to publish; none of it without `advance`.
+EpisodeHook episode_hook(EpisodeState* S, bool advance, mpc_episode_log_t* log,
+                         int32_t log_capacity) {
+  return EpisodeHook{advance ? &S->h : nullptr, log, log_capacity,
+                     advance ? S->chain_pub : nullptr, advance ? kPubWords : 0};
 }
 
 }  // namespace
@@ -365,7 +446,7 @@ static int check_args(const mpc_problem_t* p, const double* v_sc, const double* 
   if (!p || n_cand < 1 || n_steps < 1 || n_steps > MPC_MAX_STEPS || !v_sc || !beta_sc)
     return MPC_ERR_ARG;
   if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < mpc_workspace_bytes(n_cand, n_steps)) return MPC_ERR_WORKSPACE;
+  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
   return MPC_OK;
 }
 
@@ -379,9 +460,7 @@ int mpc_rollout_partials(const mpc_problem_t* p, const double* v_sc, const doubl
   Rec* part = static_cast<Rec*>(ws);
   if (states_out) {
     // CoordinateTree materialisation path: one candidate per lane, all states out.
-    dispatch_mode(integrator, [&](auto integ, auto rot) {
-      constexpr int I = decltype(integ)::value;
-      constexpr int R = decltype(rot)::value;
+    dispatch_mode(integrator, [&](auto I, auto R) {
       k_rollout_argmin<1, I, R, true, false>
           <<<rollout_grid<1>(n_cand), kBlock, 0, st>>>(
               K, nullptr, v_sc, beta_sc, n_cand, n_steps, part, states_out);
@@ -483,9 +562,7 @@ int mpc_rollout_argmin_batched(const mpc_problem_t* problems, const double* incu
   const int64_t per_robot = std::min<int64_t>(tiles, rollout_blocks(cand_per_problem));
   const dim3 grid(static_cast<unsigned>(per_robot), static_cast<unsigned>(n_problems));
   Rec* part = static_cast<Rec*>(ws);
-  dispatch_mode(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr int R = decltype(rot)::value;
+  dispatch_mode(integrator, [&](auto I, auto R) {
     if (wide)
       k_rollout_argmin_batched<kCplWide, I, R>
           <<<grid, kBlock, 0, st>>>(problems, v_sc, beta_sc, cand_per_problem, n_steps, ld, part);
@@ -494,9 +571,7 @@ int mpc_rollout_argmin_batched(const mpc_problem_t* problems, const double* incu
           <<<grid, kBlock, 0, st>>>(problems, v_sc, beta_sc, cand_per_problem, n_steps, ld, part);
   });
   if (last_hip_status() != MPC_OK) return MPC_ERR_HIP;
-  dispatch_mode(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr int R = decltype(rot)::value;
+  dispatch_mode(integrator, [&](auto I, auto R) {
     k_finalize_batched<I, R><<<n_problems, kBlock, 0, st>>>(
         part, static_cast<int>(per_robot), problems, incumbents, v_sc, beta_sc, cand_per_problem,
         n_steps, ld, out);
@@ -594,13 +669,6 @@ int mpc_episode_reset(const mpc_episode_config_t* cfg, void* state, mpc_stream_t
   return last_hip_status();
 }
 
-static int check_episode_arrays(void* state, const double* v_sc, const double* beta_sc,
-                                int64_t n_cand, int32_t n_steps) {
-  if (!state || !v_sc || !beta_sc || n_cand < 1 || n_steps < 1 || n_steps > MPC_MAX_STEPS)
-    return MPC_ERR_ARG;
-  return MPC_OK;
-}
-
 int mpc_episode_sample(const mpc_episode_config_t* cfg, void* state, double* v_sc,
                        double* beta_sc, int64_t n_cand, int32_t n_steps, int64_t index_base,
                        mpc_stream_t stream) {
@@ -653,18 +721,14 @@ int mpc_episode_generate_step(const mpc_episode_config_t* cfg, void* state, int6
   const int64_t grid = gen_grid(n_cand);
   double* part_v = reinterpret_cast<double*>(w + gen_ctl_offset(n_cand));
   double* part_b = part_v + grid * MPC_MAX_STEPS;
-  const EpisodeHook hook{&S->h, log, log_capacity, S->chain_pub, kPubWords};
-  int e;
-  const bool pl2 = frexp(cfg->L, &e) == 0.5;   // as consts_from_problem decides
-  dispatch_mode(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr int R = decltype(rot)::value;
-    if (pl2)
-      k_rollout_generated<I, R, true><<<grid, kBlock, lds, st>>>(*cfg, S, n_cand, n_steps,
-                                                                 index_base, part, part_v, part_b);
-    else
-      k_rollout_generated<I, R, false><<<grid, kBlock, lds, st>>>(*cfg, S, n_cand, n_steps,
-                                                                  index_base, part, part_v, part_b);
+  const EpisodeHook hook = episode_hook(S, true, log, log_capacity);
+  dispatch_mode(integrator, [&](auto I, auto R) {
+    dispatch_bools(
+        [&](auto PL2) {
+          k_rollout_generated<I, R, PL2><<<grid, kBlock, lds, st>>>(
+              *cfg, S, n_cand, n_steps, index_base, part, part_v, part_b);
+        },
+        length_pow2(cfg->L));
     k_finalize_gen<I, R><<<1, kFinBlock, 0, st>>>(part, static_cast<int>(grid), &S->h.K, part_v,
                                                   part_b, n_steps, index_base, &S->h.incumbent,
                                                   out, *cfg, hook);
@@ -677,7 +741,7 @@ int mpc_episode_partials(void* state, const double* v_sc, const double* beta_sc,
                          mpc_stream_t stream) {
   if (check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK) return MPC_ERR_ARG;
   if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < mpc_workspace_bytes(n_cand, n_steps)) return MPC_ERR_WORKSPACE;
+  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
   EpisodeState* S = static_cast<EpisodeState*>(state);
   launch_rollout<true>(reinterpret_cast<hipStream_t>(stream), integrator, Consts{}, &S->h.K, v_sc,
                        beta_sc, n_cand, n_steps, static_cast<Rec*>(ws));
@@ -688,26 +752,19 @@ int mpc_episode_finalize(void* state, const double* v_sc, const double* beta_sc,
                          int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
                          size_t ws_bytes, mpc_result_t* out, const mpc_episode_config_t* advance,
                          mpc_episode_log_t* log, int32_t log_capacity, mpc_stream_t stream) {
-  if (check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK || !out ||
-      index_base < 0)
-    return MPC_ERR_ARG;
-  if (mode_ok(integrator, true, true) != MPC_OK) return MPC_ERR_UNSUPPORTED;
-  // tiled controls: the flush of a tiled chained episode (its records are the
-  // chained launch's, one per tile)
-  if (is_tiled(integrator) && (!is_cum(integrator) || !advance || !tiled_ok(v_sc, beta_sc, n_cand)))
-    return MPC_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < mpc_workspace_bytes(n_cand, n_steps)) return MPC_ERR_WORKSPACE;
-  if (advance && (check_episode_cfg(advance) != MPC_OK || log_capacity < 0)) return MPC_ERR_ARG;
+  const int a = check_episode_finish(state, v_sc, beta_sc, n_cand, n_steps, index_base, integrator,
+                                     true, ws, ws_bytes, out, advance, log_capacity);
+  if (a != MPC_OK) return a;
   EpisodeState* S = static_cast<EpisodeState*>(state);
+  // (tiled controls: the records are the chained launch's, one per tile)
   const int n_part = static_cast<int>(is_tiled(integrator)
                                           ? rollout_grid<kCplWide>(n_cand)
                                           : partial_count(v_sc, beta_sc, n_cand, false));
-  const mpc_episode_config_t ecfg = advance ? *advance : mpc_episode_config_t{};
-  const EpisodeHook hook{advance ? &S->h : nullptr, log, log_capacity,
-                         advance ? S->chain_pub : nullptr, advance ? kPubWords : 0};
   launch_finalize<true>(reinterpret_cast<hipStream_t>(stream), integrator,
                         static_cast<const Rec*>(ws), n_part, Consts{}, &S->h.K, v_sc, beta_sc,
-                        n_cand, n_steps, index_base, 0.0, &S->h.incumbent, out, ecfg, hook);
+                        n_cand, n_steps, index_base, 0.0, &S->h.incumbent, out,
+                        advance ? *advance : mpc_episode_config_t{},
+                        episode_hook(S, advance != nullptr, log, log_capacity));
   return last_hip_status();
 }
 
@@ -726,21 +783,15 @@ int mpc_episode_rollout(void* state, const double* v_sc, const double* beta_sc, 
                         int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
                         size_t ws_bytes, mpc_result_t* out, const mpc_episode_config_t* advance,
                         mpc_episode_log_t* log, int32_t log_capacity, mpc_stream_t stream) {
-  if (check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK || !out ||
-      index_base < 0)
-    return MPC_ERR_ARG;
-  if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < mpc_workspace_bytes(n_cand, n_steps)) return MPC_ERR_WORKSPACE;
-  if (advance && (check_episode_cfg(advance) != MPC_OK || log_capacity < 0)) return MPC_ERR_ARG;
+  const int a = check_episode_finish(state, v_sc, beta_sc, n_cand, n_steps, index_base, integrator,
+                                     false, ws, ws_bytes, out, advance, log_capacity);
+  if (a != MPC_OK) return a;
   EpisodeState* S = static_cast<EpisodeState*>(state);
   const mpc_episode_config_t ecfg = advance ? *advance : mpc_episode_config_t{};
-  const EpisodeHook hook{advance ? &S->h : nullptr, log, log_capacity,
-                         advance ? S->chain_pub : nullptr, advance ? kPubWords : 0};
+  const EpisodeHook hook = episode_hook(S, advance != nullptr, log, log_capacity);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool wide = wide_ok(v_sc, beta_sc, n_cand);
-  dispatch_mode(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr int R = decltype(rot)::value;
+  dispatch_mode(integrator, [&](auto I, auto R) {
     if (wide)
       k_rollout_episode<kCplWide, I, R><<<fused_grid<kCplWide, I, R>(n_cand), kBlock, 0, st>>>(
           &S->h.K, v_sc, beta_sc, n_cand, n_steps, index_base, static_cast<Rec*>(ws), &S->done,
@@ -763,14 +814,13 @@ int mpc_episode_chain_step(const mpc_episode_config_t* cfg, void* state, int32_t
                            mpc_episode_log_t* log, int32_t log_capacity, mpc_stream_t stream) {
   (void)gathered;
   (void)n_gathered;
-  if (check_episode_cfg(cfg) != MPC_OK ||
-      check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK || index_base < 0 ||
-      log_capacity < 0 || mode != MPC_CHAIN_FINALIZE || epoch == 0)
+  if (!chained_args_ok(cfg, state, v_sc, beta_sc, n_cand, n_steps, index_base, log_capacity,
+                       epoch) ||
+      mode != MPC_CHAIN_FINALIZE)
     return MPC_ERR_ARG;
-  if (mode_ok(integrator, true, true) != MPC_OK || !is_cum(integrator) ||
-      !chain_ctl_ok(v_sc, beta_sc, n_cand, integrator))
+  if (!chained_mode_ok(integrator, true) || !chain_ctl_ok(v_sc, beta_sc, n_cand, integrator))
     return MPC_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < mpc_workspace_bytes(n_cand, n_steps)) return MPC_ERR_WORKSPACE;
+  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
   int has_prev = 0;
   if (v_prev) {
     if (!beta_prev || !out_prev || !ws_prev || !chain_ctl_ok(v_prev, beta_prev, n_cand, integrator))
@@ -779,27 +829,20 @@ int mpc_episode_chain_step(const mpc_episode_config_t* cfg, void* state, int32_t
   }
   if (!wall_clock_ok()) return MPC_ERR_UNSUPPORTED;
   EpisodeState* S = static_cast<EpisodeState*>(state);
-  int e;
-  const int pl2 = frexp(cfg->L, &e) == 0.5 ? 1 : 0;   // as consts_from_problem decides
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  constexpr int I = MPC_INTEG_RECT;
   // block 0 + one block per tile; the previous step's records are as many
   // (same n_cand), and as many as mpc_episode_finalize reduces
   const int64_t tiles = rollout_grid<kCplWide>(n_cand);
   const int n_part_prev = static_cast<int>(tiles);
-  auto launch = [&](auto pl2_tag, auto tiled_tag) {
-    constexpr bool P = decltype(pl2_tag)::value;
-    constexpr bool T = decltype(tiled_tag)::value;
-    k_episode_chain<I, kRotCum, kChainFin, P, T><<<tiles + 1, kBlock, 0, st>>>(
-        S, epoch, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws), has_prev,
-        static_cast<const Rec*>(ws_prev), n_part_prev, v_prev, beta_prev, index_base, out_prev,
-        nullptr, 0, *cfg, log, log_capacity, 0u);
-  };
-  const bool tl = is_tiled(integrator);
-  if (pl2)
-    tl ? launch(std::true_type{}, std::true_type{}) : launch(std::true_type{}, std::false_type{});
-  else
-    tl ? launch(std::false_type{}, std::true_type{}) : launch(std::false_type{}, std::false_type{});
+  dispatch_bools(
+      [&](auto PL2, auto TILED) {
+        k_episode_chain<MPC_INTEG_RECT, kRotCum, kChainFin, PL2, TILED>
+            <<<tiles + 1, kBlock, 0, st>>>(
+                S, epoch, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws), has_prev,
+                static_cast<const Rec*>(ws_prev), n_part_prev, v_prev, beta_prev, index_base,
+                out_prev, nullptr, 0, *cfg, log, log_capacity, 0u);
+      },
+      length_pow2(cfg->L), is_tiled(integrator));
   return last_hip_status();
 }
 
@@ -825,24 +868,21 @@ int mpc_episode_run(const mpc_episode_config_t* cfg, void* state, uint32_t epoch
                     int64_t n_cand, int32_t n_steps, int64_t index_base, int32_t integrator,
                     void* ws, size_t ws_bytes, mpc_result_t* out, mpc_episode_log_t* log,
                     int32_t log_capacity, mpc_stream_t stream) {
-  if (check_episode_cfg(cfg) != MPC_OK || !state || n_steps < 1 || n_steps > MPC_MAX_STEPS ||
-      n_cand < 2 || index_base < 0 || log_capacity < 0 || epoch0 == 0 || n_run < 1 ||
-      !v_steps || !beta_steps || !out)
+  if (!chained_args_ok(cfg, state, v_steps, beta_steps, n_cand, n_steps, index_base, log_capacity,
+                       epoch0) ||
+      n_cand < 2 || n_run < 1 || !out)
     return MPC_ERR_ARG;
   // the run's epochs are epoch0 .. epoch0 + n_run - 1, none of them 0
   if (static_cast<uint64_t>(epoch0) + static_cast<uint64_t>(n_run) - 1u > 0xFFFFFFFFull)
     return MPC_ERR_ARG;
   if (n_cand > 0x7fffffffll) return MPC_ERR_ARG;   // 32-bit local indices in the records
-  if (mode_ok(integrator, true, true) != MPC_OK || !is_cum(integrator)) return MPC_ERR_UNSUPPORTED;
+  if (!chained_mode_ok(integrator, true)) return MPC_ERR_UNSUPPORTED;
   for (int32_t j = 0; j < n_run; ++j)
     if (!v_steps[j] || !beta_steps[j] || !chain_ctl_ok(v_steps[j], beta_steps[j], n_cand, integrator))
       return MPC_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < mpc_episode_run_workspace_bytes(n_cand)) return MPC_ERR_WORKSPACE;
   if (!wall_clock_ok()) return MPC_ERR_UNSUPPORTED;
   EpisodeState* S = static_cast<EpisodeState*>(state);
-  int e;
-  const bool pl2 = frexp(cfg->L, &e) == 0.5;   // as consts_from_problem decides
-  const bool tl = is_tiled(integrator);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t tiles = cdiv(n_cand, kBlock * kCplWide);
   for (int32_t j0 = 0; j0 < n_run; j0 += kRunMaxSteps) {
@@ -865,16 +905,12 @@ int mpc_episode_run(const mpc_episode_config_t* cfg, void* state, uint32_t epoch
     ra.T = static_cast<int>(tiles);
     ra.cap = log_capacity;
     ra.ecfg = *cfg;
-    auto launch = [&](auto pl2_tag, auto tiled_tag) {
-      constexpr bool P = decltype(pl2_tag)::value;
-      constexpr bool T = decltype(tiled_tag)::value;
-      const int64_t grid = 1 + run_tile_blocks<P, T>(tiles * k);
-      k_episode_run<P, T><<<grid, kBlock, 0, st>>>(ra);
-    };
-    if (pl2)
-      tl ? launch(std::true_type{}, std::true_type{}) : launch(std::true_type{}, std::false_type{});
-    else
-      tl ? launch(std::false_type{}, std::true_type{}) : launch(std::false_type{}, std::false_type{});
+    dispatch_bools(
+        [&](auto PL2, auto TILED) {
+          const int64_t grid = 1 + run_tile_blocks<PL2, TILED>(tiles * k);
+          k_episode_run<PL2, TILED><<<grid, kBlock, 0, st>>>(ra);
+        },
+        length_pow2(cfg->L), is_tiled(integrator));
     if (hipPeekAtLastError() != hipSuccess) break;
   }
   return last_hip_status();
@@ -899,35 +935,29 @@ int mpc_episode_exchange_step2(const mpc_episode_config_t* cfg, void* state, uin
                                mpc_result_t* out_prev, mpc_candidate_t* local,
                                mpc_episode_log_t* log, int32_t log_capacity,
                                mpc_stream_t stream) {
-  if (check_episode_cfg(cfg) != MPC_OK ||
-      check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK || index_base < 0 ||
-      log_capacity < 0 || epoch == 0 || !local || !out_prev)
+  if (!chained_args_ok(cfg, state, v_sc, beta_sc, n_cand, n_steps, index_base, log_capacity,
+                       epoch) ||
+      !local || !out_prev)
     return MPC_ERR_ARG;
   // local indices travel in the low 32 bits of a tagged record
   if (n_cand > 0x7fffffffll || (gathered && n_gathered < 1)) return MPC_ERR_ARG;
   // an overlapped step stages the gathered candidates in LDS
   if (wait_tag && (!gathered || n_gathered > kXchgLdsRanks)) return MPC_ERR_ARG;
-  if (mode_ok(integrator) != MPC_OK || !is_cum(integrator) || !wide_ok(v_sc, beta_sc, n_cand))
+  if (!chained_mode_ok(integrator, false) || !wide_ok(v_sc, beta_sc, n_cand))
     return MPC_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < mpc_workspace_bytes(n_cand, n_steps)) return MPC_ERR_WORKSPACE;
+  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
   if (!wall_clock_ok()) return MPC_ERR_UNSUPPORTED;
   EpisodeState* S = static_cast<EpisodeState*>(state);
-  int e;
-  const int pl2 = frexp(cfg->L, &e) == 0.5 ? 1 : 0;
   const int64_t grid = rollout_grid<kCplWide>(n_cand) + 1;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  constexpr int I = MPC_INTEG_RECT;
-  auto launch = [&](auto pl2_tag) {
-    constexpr bool P = decltype(pl2_tag)::value;
-    k_episode_chain<I, kRotCum, kChainXchg, P><<<grid, kBlock, 0, st>>>(
-        S, epoch, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws), gathered ? 1 : 0,
-        reinterpret_cast<const Rec*>(local), 0, nullptr, nullptr, index_base, out_prev, gathered,
-        n_gathered, *cfg, log, log_capacity, gathered ? wait_tag : 0u);
-  };
-  if (pl2)
-    launch(std::true_type{});
-  else
-    launch(std::false_type{});
+  dispatch_bools(
+      [&](auto PL2) {
+        k_episode_chain<MPC_INTEG_RECT, kRotCum, kChainXchg, PL2><<<grid, kBlock, 0, st>>>(
+            S, epoch, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws), gathered ? 1 : 0,
+            reinterpret_cast<const Rec*>(local), 0, nullptr, nullptr, index_base, out_prev,
+            gathered, n_gathered, *cfg, log, log_capacity, gathered ? wait_tag : 0u);
+      },
+      length_pow2(cfg->L));
   return last_hip_status();
 }
 
@@ -1107,44 +1137,37 @@ int mpc_episode_p2p_step(const mpc_episode_config_t* cfg, void* state, uint32_t 
                          const double* beta_prev, void* mailbox, int32_t world,
                          mpc_result_t* out_prev, mpc_episode_log_t* log, int32_t log_capacity,
                          mpc_stream_t stream) {
-  if (check_episode_cfg(cfg) != MPC_OK ||
-      check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK || index_base < 0 ||
-      log_capacity < 0 || epoch == 0 || !mailbox || world < 1 || world > kMailMaxRanks)
+  if (!chained_args_ok(cfg, state, v_sc, beta_sc, n_cand, n_steps, index_base, log_capacity,
+                       epoch) ||
+      !mailbox || world < 1 || world > kMailMaxRanks)
     return MPC_ERR_ARG;
   if (prev_epoch) {
     // consecutive steps use the two mailbox slots alternately (epoch & 1)
     if (((epoch ^ prev_epoch) & 1u) == 0 || !out_prev || !ws_prev || !v_prev || !beta_prev)
       return MPC_ERR_ARG;
   }
-  if (mode_ok(integrator, true, true) != MPC_OK || !is_cum(integrator) ||
-      !chain_ctl_ok(v_sc, beta_sc, n_cand, integrator) ||
+  if (!chained_mode_ok(integrator, true) || !chain_ctl_ok(v_sc, beta_sc, n_cand, integrator) ||
       (prev_epoch && !chain_ctl_ok(v_prev, beta_prev, n_cand, integrator)))
     return MPC_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < mpc_workspace_bytes(n_cand, n_steps)) return MPC_ERR_WORKSPACE;
+  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
   if (!wall_clock_ok()) return MPC_ERR_UNSUPPORTED;
   EpisodeState* S = static_cast<EpisodeState*>(state);
-  int e;
-  const int pl2 = frexp(cfg->L, &e) == 0.5 ? 1 : 0;
   // block 0 + one block per tile; the previous step's records are as many
   const int64_t tiles = rollout_grid<kCplWide>(n_cand);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  constexpr int I = MPC_INTEG_RECT;
   // (the exchange form's argument slots: gathered = this rank's mailbox,
   // n_gathered = world, wait_tag = the previous step's epoch)
-  auto launch = [&](auto pl2_tag, auto tiled_tag) {
-    constexpr bool P = decltype(pl2_tag)::value;
-    constexpr bool T = decltype(tiled_tag)::value;
-    k_episode_chain<I, kRotCum, kChainP2P, P, T><<<tiles + 1, kBlock, 0, st>>>(
-        S, epoch, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws), prev_epoch ? 1 : 0,
-        static_cast<const Rec*>(ws_prev), static_cast<int>(tiles), v_prev, beta_prev,
-        index_base, out_prev, static_cast<const mpc_candidate_t*>(mailbox), world, *cfg, log,
-        log_capacity, prev_epoch);
-  };
-  const bool tl = is_tiled(integrator);
-  if (pl2)
-    tl ? launch(std::true_type{}, std::true_type{}) : launch(std::true_type{}, std::false_type{});
-  else
-    tl ? launch(std::false_type{}, std::true_type{}) : launch(std::false_type{}, std::false_type{});
+  dispatch_bools(
+      [&](auto PL2, auto TILED) {
+        k_episode_chain<MPC_INTEG_RECT, kRotCum, kChainP2P, PL2, TILED>
+            <<<tiles + 1, kBlock, 0, st>>>(
+                S, epoch, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws),
+                prev_epoch ? 1 : 0, static_cast<const Rec*>(ws_prev), static_cast<int>(tiles),
+                v_prev, beta_prev, index_base, out_prev,
+                static_cast<const mpc_candidate_t*>(mailbox), world, *cfg, log, log_capacity,
+                prev_epoch);
+      },
+      length_pow2(cfg->L), is_tiled(integrator));
   return last_hip_status();
 }
 
@@ -1154,28 +1177,25 @@ int mpc_episode_p2p_flush(const mpc_episode_config_t* cfg, void* state, uint32_t
                           const void* ws_last, size_t ws_bytes, void* mailbox, int32_t world,
                           mpc_result_t* out, mpc_episode_log_t* log, int32_t log_capacity,
                           mpc_stream_t stream) {
-  if (check_episode_cfg(cfg) != MPC_OK ||
-      check_episode_arrays(state, v_last, beta_last, n_cand, n_steps) != MPC_OK ||
-      index_base < 0 || !mailbox || last_epoch == 0 || world < 1 || world > kMailMaxRanks ||
-      !out || log_capacity < 0 || !ws_last)
+  // (a missing ws_last is an argument error here, not a workspace one)
+  if (!chained_args_ok(cfg, state, v_last, beta_last, n_cand, n_steps, index_base, log_capacity,
+                       last_epoch) ||
+      !mailbox || world < 1 || world > kMailMaxRanks || !out || !ws_last)
     return MPC_ERR_ARG;
-  if (mode_ok(integrator, true, true) != MPC_OK || !is_cum(integrator) ||
-      !chain_ctl_ok(v_last, beta_last, n_cand, integrator))
+  if (!chained_mode_ok(integrator, true) || !chain_ctl_ok(v_last, beta_last, n_cand, integrator))
     return MPC_ERR_UNSUPPORTED;
-  if (ws_bytes < mpc_workspace_bytes(n_cand, n_steps)) return MPC_ERR_WORKSPACE;
+  if (!workspace_ok(ws_last, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
   if (!wall_clock_ok()) return MPC_ERR_UNSUPPORTED;
-  auto launch = [&](auto tiled_tag) {
-    constexpr bool T = decltype(tiled_tag)::value;
-    k_episode_p2p_flush<MPC_INTEG_RECT, kRotCum, T>
-        <<<1, kBlock, 0, reinterpret_cast<hipStream_t>(stream)>>>(
-            *cfg, static_cast<EpisodeState*>(state), mailbox, last_epoch, world,
-            static_cast<const Rec*>(ws_last), static_cast<int>(rollout_grid<kCplWide>(n_cand)),
-            v_last, beta_last, n_cand, n_steps, index_base, out, log, log_capacity);
-  };
-  if (is_tiled(integrator))
-    launch(std::true_type{});
-  else
-    launch(std::false_type{});
+  dispatch_bools(
+      [&](auto TILED) {
+        k_episode_p2p_flush<MPC_INTEG_RECT, kRotCum, TILED>
+            <<<1, kBlock, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+                *cfg, static_cast<EpisodeState*>(state), mailbox, last_epoch, world,
+                static_cast<const Rec*>(ws_last),
+                static_cast<int>(rollout_grid<kCplWide>(n_cand)), v_last, beta_last, n_cand,
+                n_steps, index_base, out, log, log_capacity);
+      },
+      is_tiled(integrator));
   return last_hip_status();
 }
 
@@ -1332,29 +1352,12 @@ int mpc_episodes_run(void* state, int32_t n_robots, int32_t n_steps, int32_t int
   char* s = static_cast<char*>(state);
   const mpc_episode_config_t* dcfg =
       reinterpret_cast<const mpc_episode_config_t*>(s + episodes_cfg_offset(n_robots));
-#ifndef MPC_EP_VARIANT
-#define MPC_EP_VARIANT 2
-#endif
-  // 0: one 256-thread block per robot, a lane's two candidates in turn;
-  // 1: one wave per robot, its candidates two at a time (while the winner's
-  //    trajectory fits one value per lane: emit_winner's store);
-  // 2: one 256-thread block per robot, a lane's two candidates interleaved
-  const int variant = (MPC_EP_VARIANT == 1 && 3 * n_steps > 64) ? 2 : MPC_EP_VARIANT;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   RobotState* robots = reinterpret_cast<RobotState*>(s);
   const int cap = log ? log_capacity : 0;
-  dispatch_mode(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr int R = decltype(rot)::value;
-    if (variant == 1)
-      k_episodes_run<I, R, 64, true><<<n_robots, 64, 0, st>>>(dcfg, robots, n_steps, max_calls,
-                                                               log, cap, progress);
-    else if (variant == 2)
-      k_episodes_run<I, R, kBlock, true><<<n_robots, kBlock, 0, st>>>(
-          dcfg, robots, n_steps, max_calls, log, cap, progress);
-    else
-      k_episodes_run<I, R, kBlock, false><<<n_robots, kBlock, 0, st>>>(
-          dcfg, robots, n_steps, max_calls, log, cap, progress);
+  dispatch_mode(integrator, [&](auto I, auto R) {
+    k_episodes_run<I, R><<<n_robots, kBlock, 0, st>>>(dcfg, robots, n_steps, max_calls, log, cap,
+                                                      progress);
   });
   return last_hip_status();
 }
@@ -1364,25 +1367,23 @@ static size_t ft_align(size_t n) { return (n + 255) & ~static_cast<size_t>(255);
 static constexpr int64_t kFtMaxBlocks = 2048;
 static constexpr int64_t kFtMinShare = 32;   // work units per wave at least (small trees)
 
-// The current device's CU count (cached per device).
-static int64_t device_cus() {
-  static int64_t cache[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  if (cache[dev] == 0) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus < 1)
-      cus = 256;
-    cache[dev] = cus;
-  }
-  return cache[dev];
+// The workspace: the control table FtCtl[S1], the no-rotation flag word, then
+// (batched: FtRobot[n], then) the block records.
+static size_t ft_flag_offset(int64_t s1) { return ft_align(s1 * sizeof(FtCtl)); }
+static size_t ft_part_offset(int64_t s1) { return ft_flag_offset(s1) + 256; }
+static size_t ftb_robots_offset(int64_t s1) { return ft_flag_offset(s1) + 256; }
+static size_t ftb_part_offset(int64_t s1, int32_t n) {
+  return ftb_robots_offset(s1) + ft_align(n * sizeof(FtRobot));
+}
+
+// The rollout problem of a full-tree problem (its atan_target travels apart).
+static mpc_problem_t ft_problem(const mpc_fulltree_problem_t& p) {
+  return mpc_problem_t{p.x, p.y, p.phi, p.x_t, p.y_t, p.x_0, p.y_0, p.L, p.t_a, p.t_b};
 }
 
 size_t mpc_fulltree_workspace_bytes(int32_t n_v, int32_t n_beta) {
   if (n_v < 1 || n_beta < 1) return 0;
-  const size_t s1 = static_cast<size_t>(n_v) * static_cast<size_t>(n_beta);
-  return ft_align(s1 * sizeof(FtCtl)) + 256 + kFtMaxBlocks * sizeof(Rec);
+  return ft_part_offset(static_cast<int64_t>(n_v) * n_beta) + kFtMaxBlocks * sizeof(Rec);
 }
 
 int mpc_fulltree_argmin(const mpc_fulltree_problem_t* p, const double* v_grid, int32_t n_v,
@@ -1395,22 +1396,11 @@ int mpc_fulltree_argmin(const mpc_fulltree_problem_t* p, const double* v_grid, i
   if (s1 > 2000000) return MPC_ERR_ARG;  // S1^3 must fit int64 leaf indices
   if (mode_ok(integrator, false) != MPC_OK) return MPC_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < mpc_fulltree_workspace_bytes(n_v, n_beta)) return MPC_ERR_WORKSPACE;
-  mpc_problem_t q;
-  q.x = p->x;
-  q.y = p->y;
-  q.phi = p->phi;
-  q.x_t = p->x_t;
-  q.y_t = p->y_t;
-  q.x_0 = p->x_0;
-  q.y_0 = p->y_0;
-  q.L = p->L;
-  q.t_a = p->t_a;
-  q.t_b = p->t_b;
-  const Consts K = host_consts(q);
+  const Consts K = host_consts(ft_problem(*p));
   char* w = static_cast<char*>(ws);
   FtCtl* ctl = reinterpret_cast<FtCtl*>(w);
-  uint32_t* no_rot = reinterpret_cast<uint32_t*>(w + ft_align(s1 * sizeof(FtCtl)));
-  Rec* part = reinterpret_cast<Rec*>(w + ft_align(s1 * sizeof(FtCtl)) + 256);
+  uint32_t* no_rot = reinterpret_cast<uint32_t*>(w + ft_flag_offset(s1));
+  Rec* part = reinterpret_cast<Rec*>(w + ft_part_offset(s1));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (hipMemsetAsync(no_rot, 0, sizeof(uint32_t), st) != hipSuccess) return MPC_ERR_HIP;
   // the shard's contiguous range of work units (ft_units), shared out evenly
@@ -1423,9 +1413,7 @@ int mpc_fulltree_argmin(const mpc_fulltree_problem_t* p, const double* v_grid, i
   const int64_t grid = std::max<int64_t>(
       1, std::min({cdiv(u_hi - u_lo, kWaves * kFtMinShare), device_cus() * kFtWaves,
                    kFtMaxBlocks}));
-  dispatch_mode2(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr bool R = decltype(rot)::value;
+  dispatch_integ_rot(integrator, [&](auto I, auto R) {
     k_ft_controls<I><<<cdiv(s1, kBlock), kBlock, 0, st>>>(K, v_grid, beta_grid, n_beta, s1, ctl,
                                                           no_rot);
     k_ft_leaves<I, R><<<grid, kBlock, 0, st>>>(K, p->atan_target, ctl, no_rot, s1, u_lo, u_hi,
@@ -1445,7 +1433,7 @@ static int64_t ft_blocks_per_robot(int64_t s1, int32_t n) {
 size_t mpc_fulltree_batched_workspace_bytes(int32_t n_problems, int32_t n_v, int32_t n_beta) {
   if (n_problems < 1 || n_v < 1 || n_beta < 1) return 0;
   const int64_t s1 = static_cast<int64_t>(n_v) * n_beta;
-  return ft_align(s1 * sizeof(FtCtl)) + 256 + ft_align(n_problems * sizeof(FtRobot)) +
+  return ftb_part_offset(s1, n_problems) +
          static_cast<size_t>(n_problems) * ft_blocks_per_robot(s1, n_problems) * sizeof(Rec);
 }
 
@@ -1472,17 +1460,14 @@ int mpc_fulltree_argmin_batched(const mpc_fulltree_problem_t* problems,
   const Consts Kw = host_consts(q);
   char* w = static_cast<char*>(ws);
   FtCtl* ctl = reinterpret_cast<FtCtl*>(w);
-  uint32_t* no_rot = reinterpret_cast<uint32_t*>(w + ft_align(s1 * sizeof(FtCtl)));
-  FtRobot* robots = reinterpret_cast<FtRobot*>(w + ft_align(s1 * sizeof(FtCtl)) + 256);
-  Rec* part = reinterpret_cast<Rec*>(w + ft_align(s1 * sizeof(FtCtl)) + 256 +
-                                     ft_align(n_problems * sizeof(FtRobot)));
+  uint32_t* no_rot = reinterpret_cast<uint32_t*>(w + ft_flag_offset(s1));
+  FtRobot* robots = reinterpret_cast<FtRobot*>(w + ftb_robots_offset(s1));
+  Rec* part = reinterpret_cast<Rec*>(w + ftb_part_offset(s1, n_problems));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (hipMemsetAsync(no_rot, 0, sizeof(uint32_t), st) != hipSuccess) return MPC_ERR_HIP;
   const int64_t bx = ft_blocks_per_robot(s1, n_problems);
   k_ft_robots<<<cdiv(n_problems, 256), 256, 0, st>>>(problems, n_problems, L, t_a, t_b, robots);
-  dispatch_mode2(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr bool R = decltype(rot)::value;
+  dispatch_integ_rot(integrator, [&](auto I, auto R) {
     k_ft_controls<I><<<cdiv(s1, kBlock), kBlock, 0, st>>>(Kw, v_grid, beta_grid, n_beta, s1,
                                                           ctl, no_rot);
     k_ft_leaves_batched<I, R><<<dim3(static_cast<unsigned>(bx), n_problems), kBlock, 0, st>>>(
@@ -1534,18 +1519,6 @@ int mpc_fulltree_episodes_run(void* state, int32_t n_robots, const double* v_gri
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   FtEpisode* E = reinterpret_cast<FtEpisode*>(state);
   const int cap = log ? log_capacity : 0;
-#ifndef MPC_FT_LOCKSTEP
-#define MPC_FT_LOCKSTEP 1
-#endif
-  if (!MPC_FT_LOCKSTEP) {   // one block per robot, every call in one launch
-    dispatch_mode2(integrator, [&](auto integ, auto rot) {
-      constexpr int I = decltype(integ)::value;
-      constexpr bool R = decltype(rot)::value;
-      k_ft_episodes_run<I, R><<<n_robots, kBlock, 0, st>>>(
-          E, v_grid, n_v, beta_grid, n_beta, L, delta_t, eps, max_calls, log, cap, progress);
-    });
-    return last_hip_status();
-  }
   // load-balanced lockstep (mpc_ftepisodes.h): three launches per call over
   // the robots still running, the leaves of each spread over `grid` blocks
   char* s = static_cast<char*>(state);
@@ -1556,9 +1529,7 @@ int mpc_fulltree_episodes_run(void* state, int32_t n_robots, const double* v_gri
   auto* part = reinterpret_cast<Rec*>(s + ftl_part_offset(n_robots));
   const int64_t s1 = static_cast<int64_t>(n_v) * n_beta;
   const int grid = static_cast<int>(std::min<int64_t>(kFtlMaxGrid, device_cus() * kFtWaves));
-  dispatch_mode2(integrator, [&](auto integ, auto rot) {
-    constexpr int I = decltype(integ)::value;
-    constexpr bool R = decltype(rot)::value;
+  dispatch_integ_rot(integrator, [&](auto I, auto R) {
     for (int call = 0; call < max_calls; ++call) {
       k_ftl_prepare<I><<<1, kFtlPrepBlock, 0, st>>>(E, n_robots, v_grid, n_v, beta_grid, n_beta,
                                                      L, delta_t, eps, grid, ls, ctl, live,

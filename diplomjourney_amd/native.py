@@ -50,6 +50,10 @@ EXPORTS = (
     "mpc_rollout_partials_obstacles", "mpc_rollout_argmin_obstacles",
 )
 
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# The product build's flags.  The tools that compile the library (tools/resources.py,
+# asm_hazards.py, kernel_digest.py, the timeline builds) take them from here, so a tool
+# cannot analyse another build than the one that ships.
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ldl",
     # One IEEE rounding per reference operator: no a*b+c contraction.
@@ -60,8 +64,7 @@ HIPCC_FLAGS = [
 
 def build(verbose=False):
     """Compile csrc/*.hip for gfx950 into the in-tree shared library."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, *HIPCC_FLAGS, "-I", os.path.join(REPO_DIR, "include"), "-o", LIB_PATH, SRC]
+    cmd = [HIPCC, *HIPCC_FLAGS, "-I", os.path.join(REPO_DIR, "include"), "-o", LIB_PATH, SRC]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)
@@ -75,9 +78,8 @@ C_HOST_BIN = os.path.join(REPO_DIR, "tests", "_build", "exchange_episode")
 def build_c_host(verbose=False):
     """The test-side C++ host program (tests/c_host): the sharded episode
     through the C ABI and RCCL only, linked against the in-tree library."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(os.path.dirname(C_HOST_BIN), exist_ok=True)
-    cmd = [hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-I",
+    cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-I",
            os.path.join(REPO_DIR, "include"), "-o", C_HOST_BIN, C_HOST_SRC, "-L", PKG_DIR,
            "-lmpc_rollout", "-Wl,-rpath,$ORIGIN/../../diplomjourney_amd"]
     if verbose:

@@ -306,3 +306,145 @@ def test_tiled_index_header_matches_python(tmp_path):
             assert flat[o] == v[s, c] and flat[o + abi.MPC_TILE] == b[s, c]
     v2, b2 = tiled_to_soa(t, n)
     assert torch.equal(v2, v) and torch.equal(b2, b)
+
+
+def _chained_entry_calls():
+    """{entry: call(**overrides)} over fake pointers.  Every default is an
+    acceptable argument, so a case is wrong exactly where its overrides say
+    (and none may be called without an override: the call would launch)."""
+    from diplomjourney_amd.episode import reference_episode_config
+    L = native.lib()
+    cfg = reference_episode_config()
+    cfg.enumerate = 0
+    f = ctypes.c_void_p(0x1000)
+    g = ctypes.c_void_p(0x2000)
+    cum = abi.INTEGRATORS["rect+cum"]
+    base = dict(cfg=cfg, state=f, v=f, b=g, n=1024, ns=10, base=0, integ=cum, ws=f, wsb=1 << 24,
+                out=f, log=f, cap=8, epoch=3)
+
+    def entry(fn, **extra):
+        return lambda **kw: fn({**base, **extra, **kw})
+
+    def ref(c):
+        return ctypes.byref(c) if c is not None else None
+
+    def chain(a):
+        return L.mpc_episode_chain_step(
+            ref(a["cfg"]), a["state"], a["mode"], a["epoch"], a["v"], a["b"], a["n"], a["ns"],
+            a["base"], a["integ"], a["ws"], a["ws_prev"], a["wsb"], a["v_prev"], a["b_prev"],
+            a["out"], None, 0, a["log"], a["cap"], None)
+
+    def exchange2(a):
+        return L.mpc_episode_exchange_step2(
+            ref(a["cfg"]), a["state"], a["epoch"], a["wait_tag"], a["v"], a["b"], a["n"], a["ns"],
+            a["base"], a["integ"], a["ws"], a["wsb"], a["gathered"], a["n_gathered"], a["out"],
+            a["local"], a["log"], a["cap"], None)
+
+    def p2p_step(a):
+        return L.mpc_episode_p2p_step(
+            ref(a["cfg"]), a["state"], a["epoch"], a["prev"], a["v"], a["b"], a["n"], a["ns"],
+            a["base"], a["integ"], a["ws"], a["ws_prev"], a["wsb"], a["v_prev"], a["b_prev"],
+            a["mailbox"], a["world"], a["out"], a["log"], a["cap"], None)
+
+    def p2p_flush(a):
+        return L.mpc_episode_p2p_flush(
+            ref(a["cfg"]), a["state"], a["epoch"], a["v"], a["b"], a["n"], a["ns"], a["base"],
+            a["integ"], a["ws"], a["wsb"], a["mailbox"], a["world"], a["out"], a["log"], a["cap"],
+            None)
+
+    def run(a):
+        V = (ctypes.c_void_p * 2)(a["v"], a["v2"])
+        B = (ctypes.c_void_p * 2)(a["b"], a["b2"])
+        return L.mpc_episode_run(
+            ref(a["cfg"]), a["state"], a["epoch"], V, B, 2, a["n"], a["ns"], a["base"], a["integ"],
+            a["ws"], a["wsb"], a["out"], a["log"], a["cap"], None)
+
+    def generate(a):
+        return L.mpc_episode_generate_step(
+            ref(a["cfg"]), a["state"], a["n"], a["ns"], a["base"], a["integ"], a["ws"], a["wsb"],
+            a["out"], a["log"], a["cap"], None)
+
+    def fin(fn):
+        return lambda a: fn(a["state"], a["v"], a["b"], a["n"], a["ns"], a["base"], a["integ"],
+                            a["ws"], a["wsb"], a["out"], ref(a["advance"]), a["log"], a["cap"], None)
+
+    return {
+        "chain_step": entry(chain, mode=1, ws_prev=f, v_prev=None, b_prev=None),
+        "exchange_step2": entry(exchange2, wait_tag=0, gathered=None, n_gathered=0, local=f),
+        "p2p_step": entry(p2p_step, prev=2, ws_prev=f, v_prev=f, b_prev=g, mailbox=f, world=2),
+        "p2p_flush": entry(p2p_flush, mailbox=f, world=2),
+        "run": entry(run, v2=ctypes.c_void_p(0x100000), b2=ctypes.c_void_p(0x200000)),
+        "generate_step": entry(generate),
+        "finalize": entry(fin(L.mpc_episode_finalize), advance=None),
+        "rollout": entry(fin(L.mpc_episode_rollout), advance=None),
+    }
+
+
+def test_chained_entries_status_precedence_without_gpu():
+    """Which status each chained-episode entry (and finalize / rollout) returns
+    when a call is wrong in two classes at once, and for the conditions of its
+    preamble no other test reaches.  Every expected value is what the library
+    returned before the entries shared their validation helpers; every call
+    returns before any HIP call (and before the entry's wall-clock check)."""
+    from diplomjourney_amd.episode import reference_episode_config
+    A, U, W = abi.MPC_ERR_ARG, abi.MPC_ERR_UNSUPPORTED, abi.MPC_ERR_WORKSPACE
+    f = ctypes.c_void_p(0x1000)
+    odd = ctypes.c_void_p(0x2008)                      # not 16-B aligned
+    cum = abi.INTEGRATORS["rect+cum"]
+    tiled = cum | abi.MPC_LAYOUT_TILED
+    arg, integ, layout, small = dict(ns=0), dict(integ=7), dict(b=odd), dict(wsb=8)
+    enum = reference_episode_config()
+    enum.enumerate = 1
+    bad_cfg = reference_episode_config()
+    bad_cfg.stop_rule = 2
+    ok_cfg = reference_episode_config()
+    late = dict(advance=ok_cfg, cap=-1)                # finalize / rollout: checked after the workspace
+    prev = dict(v_prev=f, b_prev=None)                 # chain_step: checked after the workspace
+    two_classes = [({**arg, **integ}, A), ({**layout, **small}, U), ({**arg, **small}, A)]
+    preamble = [(dict(cap=-1), A), (dict(base=-1), A)]
+    cases = {
+        "chain_step": two_classes + preamble + [
+            (dict(epoch=0), A), (dict(mode=2), A), (dict(mode=0), A), (dict(integ=1), U),
+            (prev, A), ({**prev, **small}, W), ({**prev, **integ}, U), ({**prev, **layout}, U),
+            (dict(v_prev=f, b_prev=odd), A)],
+        "exchange_step2": two_classes + preamble + [
+            (dict(epoch=0), A), (dict(local=None), A), (dict(out=None), A), (dict(n=1 << 31), A),
+            (dict(gathered=f, n_gathered=0), A), (dict(wait_tag=1), A),
+            (dict(wait_tag=1, gathered=f, n_gathered=33), A),
+            (dict(wait_tag=1, gathered=f, n_gathered=33, integ=7), A),
+            (dict(wait_tag=1, gathered=f, n_gathered=33, wsb=8), A), (dict(integ=tiled), U)],
+        "p2p_step": two_classes + preamble + [
+            (dict(v_prev=odd), U), (dict(v_prev=odd, wsb=8), U), (dict(v_prev=None, wsb=8), A),
+            (dict(prev=1, integ=7), A), (dict(integ=1, wsb=8), U)],
+        "p2p_flush": two_classes + preamble + [
+            (dict(ws=None, integ=7), A), (dict(ws=None, wsb=8), A), (dict(integ=1, wsb=8), U)],
+        "run": two_classes + preamble + [
+            (dict(out=None), A), (dict(n=1 << 31), A), (dict(n=1 << 31, integ=7), A),
+            (dict(b2=odd), U), (dict(b2=odd, wsb=8), U), (dict(v2=None), U),
+            (dict(ws=None), W), (dict(integ=1, wsb=8), U)],
+        "generate_step": [
+            ({**arg, **integ}, A), ({**arg, **small}, A), (dict(cfg=enum, wsb=8), U),
+            (dict(n=1023, integ=7), A), (dict(n=1023, wsb=8), A), (dict(n=1023, cfg=enum), A),
+            (dict(n=1023), A), (dict(cfg=enum), U), (dict(cfg=bad_cfg), A), (dict(out=None), A),
+            ({**integ, **small}, U)] + preamble,
+        "finalize": [
+            ({**arg, **integ}, A), ({**arg, **small}, A), (dict(integ=tiled, wsb=8), U),
+            (dict(integ=tiled, advance=ok_cfg, b=odd, wsb=8), U), (dict(base=-1), A),
+            (dict(out=None), A), (late, A), ({**late, **small}, W), ({**late, **integ}, U),
+            (dict(advance=bad_cfg), A), (dict(advance=bad_cfg, wsb=8), W),
+            (dict(integ=abi.INTEGRATORS["rect"] | abi.MPC_LAYOUT_TILED, advance=ok_cfg), U)],
+        "rollout": [
+            ({**arg, **integ}, A), ({**arg, **small}, A), (dict(integ=tiled, wsb=8), U),
+            (dict(base=-1), A), (dict(out=None), A), (late, A), ({**late, **small}, W),
+            ({**late, **integ}, U), (dict(advance=bad_cfg), A), (dict(advance=bad_cfg, wsb=8), W)],
+    }
+    calls = _chained_entry_calls()
+    assert set(cases) == set(calls)
+    wrong = []
+    for name, rows in cases.items():
+        for kw, want in rows:
+            assert kw, "a call without a fault would launch"
+            got = calls[name](**kw)
+            if got != want:
+                wrong.append((name, {k: getattr(v, "value", v) for k, v in kw.items()}, got, want))
+    assert not wrong, wrong

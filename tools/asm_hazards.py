@@ -14,15 +14,16 @@ import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from diplomjourney_amd import native  # noqa: E402
+
 WAITS = 5
 
 
 def device_asm():
     out = os.path.join(tempfile.mkdtemp(), "mpc_rollout.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                    "-ffp-contract=off", "-I", os.path.join(REPO, "include"),
-                    "--cuda-device-only", "-S", "-o", out,
-                    os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_rollout.hip")],
+    subprocess.run([native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(REPO, "include"),
+                    "--cuda-device-only", "-S", "-o", out, native.SRC],
                    check=True, capture_output=True, cwd=tempfile.gettempdir())
     return out
 

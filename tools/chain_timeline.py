@@ -135,8 +135,9 @@ def build():
          "  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(mpc::g_tl), bytes) == hipSuccess ? 0 : -1;\n"
          "}\n\n// ----------------------------- RCCL exchange"),
     ])
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-           "-ldl", "-ffp-contract=off", "-I", os.path.join(d, "include"), "-o", VAR,
+    sys.path.insert(0, REPO)
+    from diplomjourney_amd import native
+    cmd = [native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(d, "include"), "-o", VAR,
            os.path.join(cs, "mpc_rollout.hip")]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=d)
     shutil.rmtree(d)

@@ -6,10 +6,11 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-       "-ffp-contract=off", "-I", os.path.join(REPO, "include"),
-       "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/resources_probe.so",
-       os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_rollout.hip")]
+sys.path.insert(0, REPO)
+from diplomjourney_amd import native  # noqa: E402
+
+cmd = [native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(REPO, "include"),
+       "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/resources_probe.so", native.SRC]
 err = subprocess.run(cmd, capture_output=True, text=True, cwd="/tmp").stderr
 pat = re.compile(sys.argv[1]) if len(sys.argv) > 1 else None
 cur = None
