@@ -1,0 +1,125 @@
+"""Batches of device-resident episodes: R robots' episodes in HBM, advanced by
+one host call for up to k MPC steps of every robot (mpc_episodes_* and
+mpc_fulltree_episodes_*)."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import native
+from .abi import (INTEGRATORS, LOG_BYTES, PROGRESS_BYTES, MpcEpisodeConfig,
+                  MpcFulltreeEpisodeConfig)
+
+# numpy view of mpc_episode_log_t (include/mpc_rollout.h), 80 bytes
+_LOG_DTYPE = [("step", "<i8"), ("index", "<i8"), ("p", "<i4"), ("episode", "<i4"),
+              ("found", "<i4"), ("status", "<i4"), ("cost", "<f8"), ("x", "<f8"), ("y", "<f8"),
+              ("phi", "<f8"), ("v", "<f8"), ("beta", "<f8")]
+
+
+class _RobotBatch:
+    """What the two batched forms share: the robots' state, per robot a log
+    ring and a progress record in HBM, and their decoding."""
+
+    def __init__(self, device, n_robots, state_bytes, integrator, log_capacity):
+        self.lib = native.lib()
+        self._C = native.calls()
+        self.R = n_robots
+        self._integ = INTEGRATORS[integrator]
+        self.state = torch.zeros(state_bytes(self.R), dtype=torch.uint8, device=device)
+        self.log_capacity = int(log_capacity)
+        self.log = torch.zeros(self.R * self.log_capacity * LOG_BYTES, dtype=torch.uint8,
+                               device=device)
+        self.progress = torch.zeros(self.R * PROGRESS_BYTES, dtype=torch.uint8, device=device)
+
+    def read_progress(self):
+        """(calls, stop, work) per robot (numpy arrays; syncs).  work: the
+        candidates (DeviceEpisodes) or leaves (DeviceFtEpisodes) rolled out."""
+        raw = self.progress.cpu().numpy()
+        p = np.frombuffer(raw.tobytes(), dtype=[("calls", "<i4"), ("stop", "<i4"),
+                                                ("candidates", "<i8")])
+        return p["calls"].copy(), p["stop"].copy(), p["candidates"].copy()
+
+    def read_logs(self, first_step=None):
+        """Per robot, its log records (numpy structured array, mpc_episode_log_t
+        fields) of steps [first, calls): first = first_step[r] if given, else
+        everything still in the ring (the last log_capacity steps)."""
+        calls, _, _ = self.read_progress()
+        raw = np.frombuffer(self.log.cpu().numpy().tobytes(), dtype=_LOG_DTYPE)
+        raw = raw.reshape(self.R, self.log_capacity)
+        out = []
+        for r in range(self.R):
+            n = int(calls[r])
+            lo = max(0, n - self.log_capacity)
+            if first_step is not None:
+                lo = max(lo, int(first_step[r]))
+            out.append(raw[r, [s % self.log_capacity for s in range(lo, n)]])
+        return out
+
+
+class DeviceEpisodes(_RobotBatch):
+    """R robots' MPC episodes in HBM (mpc_episodes_*, csrc/mpc_episodes.h):
+    one block per robot runs its episode's MPC steps back to back — the grid
+    around its control, the reference's enumeration of the step's |V| x |B|
+    constant sequences, the N-step rollout, the strict-< first minimum, the
+    winner's layer states and the episode update — so `run(k)` is ONE launch
+    for up to k MPC steps of every robot, with no host round trip and no
+    lockstep.  cfgs: one MpcEpisodeConfig per robot (start, target and rules:
+    `tree_episode_config` for run_math_model.py's loop, the reference_episode_
+    config of math_mpc for the operator scenario)."""
+
+    def __init__(self, engine, cfgs, n_steps=3, integrator="qk21", log_capacity=1024):
+        self.eng = engine
+        self.cfgs = list(cfgs)
+        self.n_steps = int(n_steps)
+        self.integrator = integrator
+        super().__init__(engine.device, len(self.cfgs), native.lib().mpc_episodes_state_bytes,
+                         integrator, log_capacity)
+        self.reset()
+
+    def reset(self):
+        arr = (MpcEpisodeConfig * self.R)(*self.cfgs)
+        self._C.mpc_episodes_reset(ctypes.byref(arr), self.R, self.state.data_ptr(),
+                                   native.current_stream())
+        self.progress.zero_()
+
+    def run(self, max_calls):
+        """Enqueue up to max_calls MPC steps of every still-running robot."""
+        self._C.mpc_episodes_run(
+            self.state.data_ptr(), self.R, self.n_steps, self._integ, int(max_calls),
+            self.log.data_ptr(), self.log_capacity, self.progress.data_ptr(),
+            native.current_stream())
+
+
+class DeviceFtEpisodes(_RobotBatch):
+    """R robots' run_math_model.py episodes with the script's own full-tree MPC
+    step, in HBM (mpc_fulltree_episodes_*, csrc/mpc_ftepisodes.h): `run(k)`
+    enqueues up to k calls of every robot with no host step in between — per
+    call the robots still running are compacted and every one's S1^3 leaves
+    are spread over the whole GPU (the load-balanced lockstep form).  cfgs:
+    MpcFulltreeEpisodeConfig per robot; v_grid / beta_grid: the script's grids
+    as device tensors."""
+
+    def __init__(self, engine, cfgs, v_grid, beta_grid, L, delta_t, eps, integrator="qk21",
+                 log_capacity=256):
+        self.cfgs = (MpcFulltreeEpisodeConfig * len(cfgs))(*cfgs)
+        self.vg, self.bg = v_grid, beta_grid
+        self.L, self.delta_t, self.eps = float(L), float(delta_t), float(eps)
+        super().__init__(engine.device, len(cfgs), native.lib().mpc_fulltree_episodes_state_bytes,
+                         integrator, log_capacity)
+        self.reset()
+
+    def reset(self):
+        self._C.mpc_fulltree_episodes_reset(ctypes.byref(self.cfgs), self.R,
+                                            self.state.data_ptr(), native.current_stream())
+        self.progress.zero_()
+
+    def run(self, max_calls):
+        """Enqueue up to max_calls MPC calls of every still-running robot
+        (three launches per call, each bounded by one call's S1^3 leaves per
+        robot spread over the GPU: no launch approaches the compute-lockup
+        timeout whatever S1 and max_calls are)."""
+        self._C.mpc_fulltree_episodes_run(
+            self.state.data_ptr(), self.R, self.vg.data_ptr(), self.vg.numel(),
+            self.bg.data_ptr(), self.bg.numel(), self.L, self.delta_t, self.eps, self._integ,
+            int(max_calls), self.log.data_ptr(), self.log_capacity, self.progress.data_ptr(),
+            native.current_stream())

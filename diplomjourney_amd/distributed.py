@@ -26,7 +26,7 @@ import math
 import torch
 import torch.distributed as dist
 
-from .abi import RESULT_BYTES, MpcResult
+from .abi import FT_RESULT_BYTES, RESULT_BYTES, MpcFulltreeResult, MpcResult
 
 
 def shard_range(n_total, rank, world):
@@ -37,18 +37,9 @@ def shard_range(n_total, rank, world):
 
 
 def gather_results(local_out, group=None):
-    """all_gather of one uint8[RESULT_BYTES] record per rank -> uint8[world*RESULT_BYTES].
-
-    RCCL (backend "nccl") gathers device memory directly.  A gloo group
-    (CPU tests, or rehearsing several ranks on one GPU) stages through host
-    memory."""
-    world = dist.get_world_size(group)
-    if local_out.is_cuda and dist.get_backend(group) == "gloo":
-        host = gather_results(local_out.cpu(), group)
-        return host.to(local_out.device)
-    gathered = torch.empty(world * RESULT_BYTES, dtype=torch.uint8, device=local_out.device)
-    dist.all_gather_into_tensor(gathered, local_out, group=group)
-    return gathered
+    """all_gather of one uint8[RESULT_BYTES] record per rank -> uint8[world*RESULT_BYTES]
+    (gather_bytes of the winner records)."""
+    return gather_bytes(local_out, group)
 
 
 def _key(res):
@@ -82,7 +73,6 @@ def select_fulltree(records, incumbent=math.inf):
     """Winner over the per-shard full-tree results (MpcFulltreeResult list or
     the all_gather'ed bytes): lexicographic (cost, global leaf) minimum, as
     the reference's single scan over j; `found` against the incumbent."""
-    from .abi import FT_RESULT_BYTES, MpcFulltreeResult
     if isinstance(records, (bytes, bytearray, memoryview)):
         raw = bytes(records)
         records = [MpcFulltreeResult.from_buffer_copy(raw[i:i + FT_RESULT_BYTES])
@@ -97,6 +87,16 @@ def select_fulltree(records, incumbent=math.inf):
     out = MpcFulltreeResult.from_buffer_copy(bytes(best))
     out.found = int(key(out)[0] == 0 and out.cost < incumbent)
     return out
+
+
+def reduce_int(value, op, group, device):
+    """`op` ("min" / "max") of one int per rank (a collective: every rank calls
+    it).  `device`: where an RCCL group reduces; a gloo group reduces on the
+    host."""
+    on_dev = dist.get_backend(group) == "nccl"
+    t = torch.tensor([int(value)], dtype=torch.int32, device=device if on_dev else "cpu")
+    dist.all_reduce(t, op={"min": dist.ReduceOp.MIN, "max": dist.ReduceOp.MAX}[op], group=group)
+    return int(t.item())
 
 
 def gather_bytes(local, group=None):

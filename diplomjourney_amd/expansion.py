@@ -12,12 +12,9 @@ import math
 import torch
 
 from . import native
-from .abi import (INTEGRATORS, MPC_MAX_STEPS, RESULT_BYTES, PROBLEM_BYTES, MpcProblem,
-                  MpcResult, make_obstacles, result_from_bytes)
-
-
-def _stream_ptr():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .abi import (FT_RESULT_BYTES, INTEGRATORS, MPC_MAX_STEPS, MPC_TILE, PROBLEM_BYTES,
+                  RESULT_BYTES, MpcFulltreeProblem, MpcFulltreeResult, MpcProblem, MpcResult,
+                  make_obstacles, result_from_bytes)
 
 
 def _integ(name_or_id):
@@ -55,6 +52,7 @@ class Expansion:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.lib = native.lib()
+        self._C = native.calls()
         self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
         self.result = torch.zeros(RESULT_BYTES, dtype=torch.uint8, device=self.device)
         self._host = torch.zeros(RESULT_BYTES, dtype=torch.uint8).pin_memory()
@@ -93,20 +91,18 @@ class Expansion:
         ws = self._workspace(ws_bytes)
         obs, n_obs = make_obstacles(obstacles)
         if n_obs or n_blocked is not None:
-            st = self.lib.mpc_rollout_argmin_obstacles(
+            self._C.mpc_rollout_argmin_obstacles(
                 ctypes.byref(problem), obs, n_obs, v_sc.data_ptr(), beta_sc.data_ptr(), n_cand,
                 n_steps, int(index_base), float(incumbent), _integ(integrator),
                 states.data_ptr() if states is not None else None,
                 ws.data_ptr(), ws.numel(), _blocked_ptr(n_blocked), out.data_ptr(),
-                _stream_ptr())
-            native.check(st, "mpc_rollout_argmin_obstacles")
+                native.current_stream())
             return out
-        st = self.lib.mpc_rollout_argmin(
+        self._C.mpc_rollout_argmin(
             ctypes.byref(problem), v_sc.data_ptr(), beta_sc.data_ptr(), n_cand, n_steps,
             int(index_base), float(incumbent), _integ(integrator),
             states.data_ptr() if states is not None else None,
-            ws.data_ptr(), ws.numel(), out.data_ptr(), _stream_ptr())
-        native.check(st, "mpc_rollout_argmin")
+            ws.data_ptr(), ws.numel(), out.data_ptr(), native.current_stream())
         return out
 
     def partials(self, problem: MpcProblem, v_sc, beta_sc, integrator="qk21", obstacles=None,
@@ -117,17 +113,14 @@ class Expansion:
         ws = self._workspace(self.lib.mpc_workspace_bytes(n_cand, n_steps))
         obs, n_obs = make_obstacles(obstacles)
         if n_obs or n_blocked is not None:
-            st = self.lib.mpc_rollout_partials_obstacles(
+            self._C.mpc_rollout_partials_obstacles(
                 ctypes.byref(problem), obs, n_obs, v_sc.data_ptr(), beta_sc.data_ptr(), n_cand,
                 n_steps, _integ(integrator), None, ws.data_ptr(), ws.numel(),
-                _blocked_ptr(n_blocked), _stream_ptr())
-            native.check(st, "mpc_rollout_partials_obstacles")
+                _blocked_ptr(n_blocked), native.current_stream())
             return
-        st = self.lib.mpc_rollout_partials(ctypes.byref(problem), v_sc.data_ptr(),
-                                           beta_sc.data_ptr(), n_cand, n_steps,
-                                           _integ(integrator), None, ws.data_ptr(), ws.numel(),
-                                           _stream_ptr())
-        native.check(st, "mpc_rollout_partials")
+        self._C.mpc_rollout_partials(ctypes.byref(problem), v_sc.data_ptr(), beta_sc.data_ptr(),
+                                     n_cand, n_steps, _integ(integrator), None, ws.data_ptr(),
+                                     ws.numel(), native.current_stream())
 
     def finalize(self, problem: MpcProblem, v_sc, beta_sc, index_base=0, incumbent=math.inf,
                  integrator="qk21", out=None):
@@ -135,12 +128,10 @@ class Expansion:
         n_steps, n_cand = v_sc.shape
         out = self.result if out is None else out
         ws = self._workspace(self.lib.mpc_workspace_bytes(n_cand, n_steps))
-        st = self.lib.mpc_rollout_finalize(ctypes.byref(problem), v_sc.data_ptr(),
-                                           beta_sc.data_ptr(), n_cand, n_steps, int(index_base),
-                                           float(incumbent), _integ(integrator), 0,
-                                           ws.data_ptr(), ws.numel(), out.data_ptr(),
-                                           _stream_ptr())
-        native.check(st, "mpc_rollout_finalize")
+        self._C.mpc_rollout_finalize(ctypes.byref(problem), v_sc.data_ptr(), beta_sc.data_ptr(),
+                                     n_cand, n_steps, int(index_base), float(incumbent),
+                                     _integ(integrator), 0, ws.data_ptr(), ws.numel(),
+                                     out.data_ptr(), native.current_stream())
         return out
 
     def fetch(self, out=None) -> MpcResult:
@@ -164,12 +155,12 @@ class Expansion:
         if out is None:
             out = torch.zeros(R * RESULT_BYTES, dtype=torch.uint8, device=self.device)
         ws = self._workspace(self.lib.mpc_batched_workspace_bytes(R, cand_per_problem, n_steps))
-        st = self.lib.mpc_rollout_argmin_batched(
+        self._C.mpc_rollout_argmin_batched(
             problems_dev.data_ptr(),
             incumbents_dev.data_ptr() if incumbents_dev is not None else None,
             R, v_sc.data_ptr(), beta_sc.data_ptr(), cand_per_problem, n_steps,
-            _integ(integrator), ws.data_ptr(), ws.numel(), out.data_ptr(), _stream_ptr())
-        native.check(st, "mpc_rollout_argmin_batched")
+            _integ(integrator), ws.data_ptr(), ws.numel(), out.data_ptr(),
+            native.current_stream())
         return out
 
     # -- multi-GPU exchange ----------------------------------------------------
@@ -177,9 +168,8 @@ class Expansion:
         """gathered: uint8 CUDA tensor of n * sizeof(mpc_result_t) (all_gather output)."""
         n = gathered.numel() // RESULT_BYTES
         out = self.result if out is None else out
-        st = self.lib.mpc_select_winner(gathered.data_ptr(), n, float(incumbent),
-                                        out.data_ptr(), _stream_ptr())
-        native.check(st, "mpc_select_winner")
+        self._C.mpc_select_winner(gathered.data_ptr(), n, float(incumbent), out.data_ptr(),
+                                  native.current_stream())
         return out
 
     # -- synthetic candidates --------------------------------------------------
@@ -189,11 +179,10 @@ class Expansion:
             v_out = torch.empty((n_steps, n_cand), dtype=torch.float64, device=self.device)
             beta_out = torch.empty_like(v_out)
         ld = v_out.shape[1] if ld is None else ld
-        st = self.lib.mpc_sample_controls(
+        self._C.mpc_sample_controls(
             v_grid.data_ptr(), v_grid.numel(), beta_grid.data_ptr(), beta_grid.numel(),
             n_cand, n_steps, int(seed) & 0xFFFFFFFFFFFFFFFF, int(index_base), int(const_prefix),
-            v_out.data_ptr(), beta_out.data_ptr(), ld, _stream_ptr())
-        native.check(st, "mpc_sample_controls")
+            v_out.data_ptr(), beta_out.data_ptr(), ld, native.current_stream())
         return v_out, beta_out
 
     def sample_controls_tiled(self, v_grid, beta_grid, n_cand, n_steps, seed, index_base=0,
@@ -201,14 +190,12 @@ class Expansion:
         """The same candidates as sample_controls in the TILED layout
         (MPC_LAYOUT_TILED): a tensor [tiles, n_steps, 2, MPC_TILE] (v then
         beta per tile and step); tiled_to_soa() gives the SoA view's values."""
-        from .abi import MPC_TILE
         tiles = -(-n_cand // MPC_TILE)
         out = torch.empty((tiles, n_steps, 2, MPC_TILE), dtype=torch.float64, device=self.device)
-        st = self.lib.mpc_sample_controls_tiled(
+        self._C.mpc_sample_controls_tiled(
             v_grid.data_ptr(), v_grid.numel(), beta_grid.data_ptr(), beta_grid.numel(),
             n_cand, n_steps, int(seed) & 0xFFFFFFFFFFFFFFFF, int(index_base), int(const_prefix),
-            out.data_ptr(), _stream_ptr())
-        native.check(st, "mpc_sample_controls_tiled")
+            out.data_ptr(), native.current_stream())
         return out
 
 
@@ -223,7 +210,6 @@ def tiled_to_soa(tiles, n_cand):
 def soa_to_tiled(v, beta):
     """The tiled tensor [tiles, n_steps, 2, MPC_TILE] of SoA controls (the last
     tile padded with copies of the last candidate)."""
-    from .abi import MPC_TILE
     ns, n = v.shape
     tiles = -(-n // MPC_TILE)
     pad = tiles * MPC_TILE - n
@@ -239,16 +225,13 @@ def fulltree_argmin(engine, problem, v_grid, beta_grid, incumbent, integrator="q
     device grids v_grid [|V|], beta_grid [|B|] (fp64 tensors on the engine's
     device); this call evaluates leaf shard `shard` of `n_shards`.  Returns
     the device result buffer (uint8[FT_RESULT_BYTES])."""
-    from .abi import FT_RESULT_BYTES
-    lib = engine.lib
+    lib, C = engine.lib, native.calls()
     nv, nb = v_grid.numel(), beta_grid.numel()
     ws = engine._workspace(lib.mpc_fulltree_workspace_bytes(nv, nb))
     out = torch.empty(FT_RESULT_BYTES, dtype=torch.uint8, device=engine.device)
-    st = lib.mpc_fulltree_argmin(ctypes.byref(problem), v_grid.data_ptr(), nv,
-                                 beta_grid.data_ptr(), nb, float(incumbent),
-                                 _integ(integrator), int(shard), int(n_shards), ws.data_ptr(),
-                                 ws.numel(), out.data_ptr(), _stream_ptr())
-    native.check(st, "mpc_fulltree_argmin")
+    C.mpc_fulltree_argmin(ctypes.byref(problem), v_grid.data_ptr(), nv, beta_grid.data_ptr(), nb,
+                          float(incumbent), _integ(integrator), int(shard), int(n_shards),
+                          ws.data_ptr(), ws.numel(), out.data_ptr(), native.current_stream())
     return out
 
 
@@ -257,30 +240,26 @@ def fulltree_argmin_batched(engine, problems_dev, incumbents_dev, L, t_a, t_b, v
     """R robots' full trees (one per run_math_model episode, lockstep):
     problems_dev uint8[R * sizeof(mpc_fulltree_problem_t)], incumbents_dev
     float64[R]; returns the device results uint8[R * FT_RESULT_BYTES]."""
-    from .abi import FT_RESULT_BYTES, MpcFulltreeProblem
-    lib = engine.lib
+    lib, C = engine.lib, native.calls()
     R = problems_dev.numel() // ctypes.sizeof(MpcFulltreeProblem)
     nv, nb = v_grid.numel(), beta_grid.numel()
     ws = engine._workspace(lib.mpc_fulltree_batched_workspace_bytes(R, nv, nb))
     if out is None:
         out = torch.empty(R * FT_RESULT_BYTES, dtype=torch.uint8, device=engine.device)
-    st = lib.mpc_fulltree_argmin_batched(
+    C.mpc_fulltree_argmin_batched(
         problems_dev.data_ptr(), incumbents_dev.data_ptr(), R, float(L), float(t_a),
         float(t_b), v_grid.data_ptr(), nv, beta_grid.data_ptr(), nb, _integ(integrator),
-        ws.data_ptr(), ws.numel(), out.data_ptr(), _stream_ptr())
-    native.check(st, "mpc_fulltree_argmin_batched")
+        ws.data_ptr(), ws.numel(), out.data_ptr(), native.current_stream())
     return out
 
 
 def fulltree_results(out_dev):
-    from .abi import FT_RESULT_BYTES, MpcFulltreeResult
     raw = out_dev.cpu().numpy().tobytes()
     return [MpcFulltreeResult.from_buffer_copy(raw[i:i + FT_RESULT_BYTES])
             for i in range(0, len(raw), FT_RESULT_BYTES)]
 
 
 def fulltree_result(out_dev):
-    from .abi import MpcFulltreeResult
     return MpcFulltreeResult.from_buffer_copy(out_dev.cpu().numpy().tobytes())
 
 

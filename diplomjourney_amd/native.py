@@ -3,14 +3,22 @@
 The product path has no CPU fallback: if the in-tree library is missing or a
 call returns a non-zero status, this module raises.  Device buffers come from
 PyTorch-ROCm tensors (`tensor.data_ptr()`), the stream from
-`torch.cuda.current_stream().cuda_stream`.  torch is imported first so the
-library's libamdhip64.so.7 dependency resolves to the runtime torch already
-loaded (one HIP runtime per process).
+`native.current_stream()`.  torch is imported first so the library's
+libamdhip64.so.7 dependency resolves to the runtime torch already loaded (one
+HIP runtime per process).
+
+PROTOTYPES holds every entry's signature (tests/test_abi.py compares it with
+the header).  Two handles are made from it: `lib()`, whose entries return their
+status, and `calls()`, whose entries raise MpcError(status, entry name).
 """
 import ctypes
 import os
 import subprocess
 import sys
+import types
+from ctypes import POINTER, c_char_p, c_int, c_size_t, c_uint32, c_uint64
+
+import torch  # before the library loads: one HIP runtime, torch's libamdhip64.so.7
 
 from .abi import MpcEpisodeConfig, MpcError, MpcFulltreeProblem, MpcProblem
 
@@ -21,34 +29,111 @@ LIB_PATH = os.path.join(PKG_DIR, LIB_NAME)
 SRC = os.path.join(PKG_DIR, "csrc", "mpc_rollout.hip")
 HEADER = os.path.join(REPO_DIR, "include", "mpc_rollout.h")
 
+_P = ctypes.c_void_p           # any device / host pointer, mpc_stream_t, mpc_comm_t
+_PP = POINTER(_P)              # pointer arrays and handle out-parameters (byref)
+_I32 = ctypes.c_int32
+_I64 = ctypes.c_int64
+_D = ctypes.c_double
+_PROB = POINTER(MpcProblem)
+_CFG = POINTER(MpcEpisodeConfig)
+# mpc_episode_finalize / _step / _rollout: one signature
+_FINALIZE = [_P, _P, _P, _I64, _I32, _I64, _I32, _P, c_size_t, _P, _CFG, _P, _I32, _P]
+
+# entry -> (restype, argtypes): every function include/mpc_rollout.h declares
+PROTOTYPES = {
+    "mpc_version": (c_char_p, []),
+    "mpc_strerror": (c_char_p, [c_int]),
+    "mpc_workspace_bytes": (c_size_t, [_I64, _I32]),
+    "mpc_rollout_argmin": (c_int, [_PROB, _P, _P, _I64, _I32, _I64, _D, _I32, _P, _P, c_size_t,
+                                   _P, _P]),
+    "mpc_rollout_partials": (c_int, [_PROB, _P, _P, _I64, _I32, _I32, _P, _P, c_size_t, _P]),
+    "mpc_rollout_finalize": (c_int, [_PROB, _P, _P, _I64, _I32, _I64, _D, _I32, _I32, _P,
+                                     c_size_t, _P, _P]),
+    "mpc_rollout_partials_obstacles": (c_int, [_PROB, _P, _I32, _P, _P, _I64, _I32, _I32, _P, _P,
+                                               c_size_t, _P, _P]),
+    "mpc_rollout_argmin_obstacles": (c_int, [_PROB, _P, _I32, _P, _P, _I64, _I32, _I64, _D, _I32,
+                                             _P, _P, c_size_t, _P, _P, _P]),
+    "mpc_batched_workspace_bytes": (c_size_t, [_I32, _I64, _I32]),
+    "mpc_rollout_argmin_batched": (c_int, [_P, _P, _I32, _P, _P, _I64, _I32, _I32, _P, c_size_t,
+                                           _P, _P]),
+    "mpc_select_winner": (c_int, [_P, _I32, _D, _P, _P]),
+    "mpc_stream_probe": (c_int, [_P, _P, _I64, _I32, _P, c_size_t, _P]),
+    "mpc_stream_probe_tiled": (c_int, [_P, _I64, _I32, _P, c_size_t, _P]),
+    "mpc_rcp_estimate": (c_int, [_P, _P, _I64, _P]),
+    "mpc_sample_controls": (c_int, [_P, _I32, _P, _I32, _I64, _I32, c_uint64, _I64, _I32, _P, _P,
+                                    _I64, _P]),
+    "mpc_sample_controls_tiled": (c_int, [_P, _I32, _P, _I32, _I64, _I32, c_uint64, _I64, _I32,
+                                          _P, _P]),
+    # the device-resident episode
+    "mpc_episode_state_bytes": (c_size_t, []),
+    "mpc_episode_reset": (c_int, [_CFG, _P, _P]),
+    "mpc_episode_expand": (c_int, [_CFG, _P, _P, _P, _I64, _I32, _I64, _I32, _P, c_size_t, _P,
+                                   _P]),
+    "mpc_episode_advance": (c_int, [_CFG, _P, _P, _I32, _P, _I32, _P]),
+    "mpc_episode_rollout": (c_int, _FINALIZE),
+    "mpc_episode_sample": (c_int, [_CFG, _P, _P, _P, _I64, _I32, _I64, _P]),
+    "mpc_episode_partials": (c_int, [_P, _P, _P, _I64, _I32, _I32, _P, c_size_t, _P]),
+    "mpc_episode_finalize": (c_int, _FINALIZE),
+    "mpc_episode_step": (c_int, _FINALIZE),
+    "mpc_episode_chain_step": (c_int, [_CFG, _P, _I32, c_uint32, _P, _P, _I64, _I32, _I64, _I32,
+                                       _P, _P, c_size_t, _P, _P, _P, _P, _I32, _P, _I32, _P]),
+    "mpc_episode_run_workspace_bytes": (c_size_t, [_I64]),
+    "mpc_episode_run": (c_int, [_CFG, _P, c_uint32, _PP, _PP, _I32, _I64, _I32, _I64, _I32, _P,
+                                c_size_t, _P, _P, _I32, _P]),
+    "mpc_episode_exchange_step": (c_int, [_CFG, _P, c_uint32, _P, _P, _I64, _I32, _I64, _I32, _P,
+                                          c_size_t, _P, _I32, _P, _P, _P, _I32, _P]),
+    "mpc_episode_exchange_step2": (c_int, [_CFG, _P, c_uint32, c_uint32, _P, _P, _I64, _I32, _I64,
+                                           _I32, _P, c_size_t, _P, _I32, _P, _P, _P, _I32, _P]),
+    "mpc_episode_exchange_mark": (c_int, [_P, c_uint32, _P]),
+    "mpc_episode_exchange_flush": (c_int, [_CFG, _P, _I32, _P, _I32, _P, _P, _I32, _P]),
+    "mpc_episode_chain_error": (c_int, [_P, POINTER(_I32), _P]),
+    "mpc_episode_generate_workspace_bytes": (c_size_t, [_I64, _I32]),
+    "mpc_episode_generate_step": (c_int, [_CFG, _P, _I64, _I32, _I64, _I32, _P, c_size_t, _P, _P,
+                                          _I32, _P]),
+    # CU-masked launch streams
+    "mpc_stream_create_cu_reserved": (c_int, [_I32, _PP]),
+    "mpc_stream_create_cu_share": (c_int, [_I32, _I32, _PP]),
+    "mpc_stream_destroy": (c_int, [_P]),
+    # the P2P mailbox exchange
+    "mpc_mailbox_bytes": (c_size_t, [_I32]),
+    "mpc_mailbox_alloc": (c_int, [_I32, _I32, _PP]),
+    "mpc_mailbox_free": (c_int, [_P]),
+    "mpc_mailbox_set_peers": (c_int, [_P, _I32, _I32, _PP]),
+    "mpc_mailbox_ping": (c_int, [_P, c_uint32, _P, _P]),
+    "mpc_mailbox_clear": (c_int, [_P, _I32, _P]),
+    "mpc_ipc_handle": (c_int, [_P, _P]),
+    "mpc_ipc_open": (c_int, [_P, _PP]),
+    "mpc_ipc_close": (c_int, [_P]),
+    "mpc_peer_enable": (c_int, [_I32]),
+    "mpc_episode_p2p_step": (c_int, [_CFG, _P, c_uint32, c_uint32, _P, _P, _I64, _I32, _I64, _I32,
+                                     _P, _P, c_size_t, _P, _P, _P, _I32, _P, _P, _I32, _P]),
+    "mpc_episode_p2p_flush": (c_int, [_CFG, _P, c_uint32, _P, _P, _I64, _I32, _I64, _I32, _P,
+                                      c_size_t, _P, _I32, _P, _P, _I32, _P]),
+    # the RCCL exchange of a non-Python host (tests/c_host)
+    "mpc_comm_unique_id": (c_int, [_P]),
+    "mpc_comm_init_rank": (c_int, [_P, _I32, _I32, _PP]),
+    "mpc_comm_init_all": (c_int, [_I32, POINTER(_I32), _PP]),
+    "mpc_comm_destroy": (c_int, [_P]),
+    "mpc_exchange_allgather": (c_int, [_P, _P, _P, _P]),
+    "mpc_exchange_allgather_group": (c_int, [_I32, _PP, _PP, _PP, _PP]),
+    # the full tree and the batched episodes
+    "mpc_fulltree_workspace_bytes": (c_size_t, [_I32, _I32]),
+    "mpc_fulltree_argmin": (c_int, [POINTER(MpcFulltreeProblem), _P, _I32, _P, _I32, _D, _I32,
+                                    _I32, _I32, _P, c_size_t, _P, _P]),
+    "mpc_fulltree_batched_workspace_bytes": (c_size_t, [_I32, _I32, _I32]),
+    "mpc_fulltree_argmin_batched": (c_int, [_P, _P, _I32, _D, _D, _D, _P, _I32, _P, _I32, _I32,
+                                            _P, c_size_t, _P, _P]),
+    "mpc_episodes_state_bytes": (c_size_t, [_I32]),
+    "mpc_episodes_reset": (c_int, [_P, _I32, _P, _P]),
+    "mpc_episodes_run": (c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
+    "mpc_fulltree_episodes_state_bytes": (c_size_t, [_I32]),
+    "mpc_fulltree_episodes_reset": (c_int, [_P, _I32, _P, _P]),
+    "mpc_fulltree_episodes_run": (c_int, [_P, _I32, _P, _I32, _P, _I32, _D, _D, _D, _I32, _I32,
+                                          _P, _I32, _P, _P]),
+}
+
 # Every symbol include/mpc_rollout.h declares (checked by tests/test_abi.py).
-EXPORTS = (
-    "mpc_version", "mpc_strerror", "mpc_workspace_bytes", "mpc_rollout_argmin",
-    "mpc_rollout_partials", "mpc_rollout_finalize",
-    "mpc_batched_workspace_bytes", "mpc_rollout_argmin_batched", "mpc_select_winner",
-    "mpc_stream_probe", "mpc_rcp_estimate",
-    "mpc_sample_controls", "mpc_episode_state_bytes", "mpc_episode_reset",
-    "mpc_episode_expand", "mpc_episode_advance", "mpc_episode_sample", "mpc_episode_partials",
-    "mpc_episode_finalize", "mpc_episode_rollout", "mpc_episode_step", "mpc_episode_chain_step",
-    "mpc_episode_chain_error", "mpc_episode_exchange_step", "mpc_episode_exchange_flush",
-    "mpc_comm_unique_id", "mpc_comm_init_rank", "mpc_comm_init_all", "mpc_comm_destroy",
-    "mpc_exchange_allgather", "mpc_exchange_allgather_group",
-    "mpc_episode_generate_workspace_bytes", "mpc_episode_generate_step",
-    "mpc_fulltree_workspace_bytes", "mpc_fulltree_argmin",
-    "mpc_fulltree_batched_workspace_bytes", "mpc_fulltree_argmin_batched",
-    "mpc_episodes_state_bytes", "mpc_episodes_reset", "mpc_episodes_run",
-    "mpc_episode_exchange_step2", "mpc_episode_exchange_mark",
-    "mpc_stream_create_cu_reserved", "mpc_stream_create_cu_share", "mpc_stream_destroy",
-    "mpc_mailbox_bytes", "mpc_mailbox_alloc", "mpc_mailbox_free", "mpc_mailbox_set_peers",
-    "mpc_mailbox_ping", "mpc_mailbox_clear",
-    "mpc_ipc_handle",
-    "mpc_ipc_open", "mpc_ipc_close", "mpc_peer_enable", "mpc_episode_p2p_step",
-    "mpc_episode_p2p_flush",
-    "mpc_fulltree_episodes_state_bytes", "mpc_fulltree_episodes_reset",
-    "mpc_fulltree_episodes_run", "mpc_stream_probe_tiled", "mpc_sample_controls_tiled",
-    "mpc_episode_run_workspace_bytes", "mpc_episode_run",
-    "mpc_rollout_partials_obstacles", "mpc_rollout_argmin_obstacles",
-)
+EXPORTS = tuple(PROTOTYPES)
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # The product build's flags.  The tools that compile the library (tools/resources.py,
@@ -97,181 +182,55 @@ def needs_build():
 
 
 _lib = None
-
-_P = ctypes.c_void_p
-_I32 = ctypes.c_int32
-_I64 = ctypes.c_int64
-_D = ctypes.c_double
+_calls = None
 
 
 def lib():
-    """Load the HIP library (raises if it was not built)."""
+    """Load the HIP library (raises if it was not built).  Its entries return
+    their status: for the callers that inspect one."""
     global _lib
     if _lib is not None:
         return _lib
-    import torch  # noqa: F401  (one HIP runtime: torch's libamdhip64.so.7)
     path = LIB_PATH
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run __graft_entry__.build() "
                            "(the MPC expansion has no CPU fallback)")
     L = ctypes.CDLL(path)
-    L.mpc_version.restype = ctypes.c_char_p
-    L.mpc_version.argtypes = []
-    L.mpc_strerror.restype = ctypes.c_char_p
-    L.mpc_strerror.argtypes = [ctypes.c_int]
-    L.mpc_workspace_bytes.restype = ctypes.c_size_t
-    L.mpc_workspace_bytes.argtypes = [_I64, _I32]
-    L.mpc_rollout_argmin.restype = ctypes.c_int
-    L.mpc_rollout_argmin.argtypes = [ctypes.POINTER(MpcProblem), _P, _P, _I64, _I32, _I64, _D,
-                                     _I32, _P, _P, ctypes.c_size_t, _P, _P]
-    L.mpc_rollout_partials.restype = ctypes.c_int
-    L.mpc_rollout_partials.argtypes = [ctypes.POINTER(MpcProblem), _P, _P, _I64, _I32, _I32, _P,
-                                       _P, ctypes.c_size_t, _P]
-    L.mpc_rollout_finalize.restype = ctypes.c_int
-    L.mpc_rollout_finalize.argtypes = [ctypes.POINTER(MpcProblem), _P, _P, _I64, _I32, _I64, _D,
-                                       _I32, _I32, _P, ctypes.c_size_t, _P, _P]
-    L.mpc_rollout_partials_obstacles.restype = ctypes.c_int
-    L.mpc_rollout_partials_obstacles.argtypes = [ctypes.POINTER(MpcProblem), _P, _I32, _P, _P, _I64,
-                                                 _I32, _I32, _P, _P, ctypes.c_size_t, _P, _P]
-    L.mpc_rollout_argmin_obstacles.restype = ctypes.c_int
-    L.mpc_rollout_argmin_obstacles.argtypes = [ctypes.POINTER(MpcProblem), _P, _I32, _P, _P, _I64,
-                                               _I32, _I64, _D, _I32, _P, _P, ctypes.c_size_t, _P,
-                                               _P, _P]
-    L.mpc_batched_workspace_bytes.restype = ctypes.c_size_t
-    L.mpc_batched_workspace_bytes.argtypes = [_I32, _I64, _I32]
-    L.mpc_rollout_argmin_batched.restype = ctypes.c_int
-    L.mpc_rollout_argmin_batched.argtypes = [_P, _P, _I32, _P, _P, _I64, _I32, _I32, _P,
-                                             ctypes.c_size_t, _P, _P]
-    L.mpc_stream_probe.restype = ctypes.c_int
-    L.mpc_stream_probe.argtypes = [_P, _P, _I64, _I32, _P, ctypes.c_size_t, _P]
-    L.mpc_stream_probe_tiled.restype = ctypes.c_int
-    L.mpc_stream_probe_tiled.argtypes = [_P, _I64, _I32, _P, ctypes.c_size_t, _P]
-    L.mpc_sample_controls_tiled.restype = ctypes.c_int
-    L.mpc_sample_controls_tiled.argtypes = [_P, _I32, _P, _I32, _I64, _I32, ctypes.c_uint64,
-                                            _I64, _I32, _P, _P]
-    L.mpc_rcp_estimate.restype = ctypes.c_int
-    L.mpc_rcp_estimate.argtypes = [_P, _P, _I64, _P]
-    L.mpc_select_winner.restype = ctypes.c_int
-    L.mpc_select_winner.argtypes = [_P, _I32, _D, _P, _P]
-    L.mpc_sample_controls.restype = ctypes.c_int
-    L.mpc_sample_controls.argtypes = [_P, _I32, _P, _I32, _I64, _I32, ctypes.c_uint64, _I64,
-                                      _I32, _P, _P, _I64, _P]
-    L.mpc_episode_state_bytes.restype = ctypes.c_size_t
-    L.mpc_episode_state_bytes.argtypes = []
-    L.mpc_episode_reset.restype = ctypes.c_int
-    L.mpc_episode_reset.argtypes = [ctypes.POINTER(MpcEpisodeConfig), _P, _P]
-    L.mpc_episode_expand.restype = ctypes.c_int
-    L.mpc_episode_expand.argtypes = [ctypes.POINTER(MpcEpisodeConfig), _P, _P, _P, _I64, _I32,
-                                     _I64, _I32, _P, ctypes.c_size_t, _P, _P]
-    L.mpc_episode_advance.restype = ctypes.c_int
-    L.mpc_episode_advance.argtypes = [ctypes.POINTER(MpcEpisodeConfig), _P, _P, _I32, _P, _I32,
-                                      _P]
-    L.mpc_episode_sample.restype = ctypes.c_int
-    L.mpc_episode_sample.argtypes = [ctypes.POINTER(MpcEpisodeConfig), _P, _P, _P, _I64, _I32,
-                                     _I64, _P]
-    L.mpc_episode_partials.restype = ctypes.c_int
-    L.mpc_episode_partials.argtypes = [_P, _P, _P, _I64, _I32, _I32, _P, ctypes.c_size_t, _P]
-    L.mpc_episode_finalize.restype = ctypes.c_int
-    L.mpc_episode_finalize.argtypes = [_P, _P, _P, _I64, _I32, _I64, _I32, _P, ctypes.c_size_t,
-                                       _P, ctypes.POINTER(MpcEpisodeConfig), _P, _I32, _P]
-    L.mpc_fulltree_workspace_bytes.restype = ctypes.c_size_t
-    L.mpc_fulltree_workspace_bytes.argtypes = [_I32, _I32]
-    L.mpc_fulltree_argmin.restype = ctypes.c_int
-    L.mpc_fulltree_argmin.argtypes = [ctypes.POINTER(MpcFulltreeProblem), _P, _I32, _P, _I32,
-                                      ctypes.c_double, _I32, _I32, _I32, _P, ctypes.c_size_t,
-                                      _P, _P]
-    L.mpc_fulltree_batched_workspace_bytes.restype = ctypes.c_size_t
-    L.mpc_fulltree_batched_workspace_bytes.argtypes = [_I32, _I32, _I32]
-    L.mpc_fulltree_argmin_batched.restype = ctypes.c_int
-    L.mpc_fulltree_argmin_batched.argtypes = [_P, _P, _I32, ctypes.c_double, ctypes.c_double,
-                                              ctypes.c_double, _P, _I32, _P, _I32, _I32, _P,
-                                              ctypes.c_size_t, _P, _P]
-    L.mpc_episode_step.restype = ctypes.c_int
-    L.mpc_episode_step.argtypes = L.mpc_episode_finalize.argtypes
-    L.mpc_episode_chain_step.restype = ctypes.c_int
-    L.mpc_episode_chain_step.argtypes = [ctypes.POINTER(MpcEpisodeConfig), _P, _I32,
-                                         ctypes.c_uint32, _P, _P,
-                                         _I64, _I32, _I64, _I32, _P, _P, ctypes.c_size_t, _P,
-                                         _P, _P, _P, _I32, _P, _I32, _P]
-    L.mpc_episode_run_workspace_bytes.restype = ctypes.c_size_t
-    L.mpc_episode_run_workspace_bytes.argtypes = [_I64]
-    L.mpc_episode_run.restype = ctypes.c_int
-    L.mpc_episode_run.argtypes = [ctypes.POINTER(MpcEpisodeConfig), _P, ctypes.c_uint32,
-                                  ctypes.POINTER(_P), ctypes.POINTER(_P), _I32, _I64, _I32, _I64,
-                                  _I32, _P, ctypes.c_size_t, _P, _P, _I32, _P]
-    L.mpc_episode_exchange_step.restype = ctypes.c_int
-    L.mpc_episode_exchange_step.argtypes = [ctypes.POINTER(MpcEpisodeConfig), _P, ctypes.c_uint32,
-                                            _P, _P, _I64, _I32, _I64, _I32, _P, ctypes.c_size_t,
-                                            _P, _I32, _P, _P, _P, _I32, _P]
-    L.mpc_episode_exchange_step2.restype = ctypes.c_int
-    L.mpc_episode_exchange_step2.argtypes = [
-        ctypes.POINTER(MpcEpisodeConfig), _P, ctypes.c_uint32, ctypes.c_uint32, _P, _P, _I64,
-        _I32, _I64, _I32, _P, ctypes.c_size_t, _P, _I32, _P, _P, _P, _I32, _P]
-    L.mpc_episode_exchange_mark.restype = ctypes.c_int
-    L.mpc_episode_exchange_mark.argtypes = [_P, ctypes.c_uint32, _P]
-    L.mpc_stream_create_cu_reserved.restype = ctypes.c_int
-    L.mpc_stream_create_cu_reserved.argtypes = [_I32, ctypes.POINTER(_P)]
-    L.mpc_stream_create_cu_share.restype = ctypes.c_int
-    L.mpc_stream_create_cu_share.argtypes = [_I32, _I32, ctypes.POINTER(_P)]
-    L.mpc_stream_destroy.restype = ctypes.c_int
-    L.mpc_stream_destroy.argtypes = [_P]
-    L.mpc_episode_exchange_flush.restype = ctypes.c_int
-    L.mpc_episode_exchange_flush.argtypes = [ctypes.POINTER(MpcEpisodeConfig), _P, _I32, _P, _I32,
-                                             _P, _P, _I32, _P]
-    L.mpc_episode_chain_error.restype = ctypes.c_int
-    L.mpc_episode_chain_error.argtypes = [_P, ctypes.POINTER(_I32), _P]
-    L.mpc_episode_generate_workspace_bytes.restype = ctypes.c_size_t
-    L.mpc_episode_generate_workspace_bytes.argtypes = [_I64, _I32]
-    L.mpc_episode_generate_step.restype = ctypes.c_int
-    L.mpc_episode_generate_step.argtypes = [ctypes.POINTER(MpcEpisodeConfig), _P, _I64, _I32,
-                                            _I64, _I32, _P, ctypes.c_size_t, _P, _P, _I32, _P]
-    L.mpc_episode_rollout.restype = ctypes.c_int
-    L.mpc_episode_rollout.argtypes = [_P, _P, _P, _I64, _I32, _I64, _I32, _P, ctypes.c_size_t,
-                                      _P, ctypes.POINTER(MpcEpisodeConfig), _P, _I32, _P]
-    L.mpc_mailbox_bytes.restype = ctypes.c_size_t
-    L.mpc_mailbox_bytes.argtypes = [_I32]
-    L.mpc_mailbox_alloc.restype = ctypes.c_int
-    L.mpc_mailbox_alloc.argtypes = [_I32, _I32, ctypes.POINTER(_P)]
-    L.mpc_mailbox_free.restype = ctypes.c_int
-    L.mpc_mailbox_free.argtypes = [_P]
-    L.mpc_ipc_handle.restype = ctypes.c_int
-    L.mpc_ipc_handle.argtypes = [_P, _P]
-    L.mpc_ipc_open.restype = ctypes.c_int
-    L.mpc_ipc_open.argtypes = [_P, ctypes.POINTER(_P)]
-    L.mpc_ipc_close.restype = ctypes.c_int
-    L.mpc_ipc_close.argtypes = [_P]
-    L.mpc_peer_enable.restype = ctypes.c_int
-    L.mpc_peer_enable.argtypes = [_I32]
-    L.mpc_mailbox_ping.restype = ctypes.c_int
-    L.mpc_mailbox_ping.argtypes = [_P, ctypes.c_uint32, _P, _P]
-    L.mpc_mailbox_clear.restype = ctypes.c_int
-    L.mpc_mailbox_clear.argtypes = [_P, _I32, _P]
-    L.mpc_mailbox_set_peers.restype = ctypes.c_int
-    L.mpc_mailbox_set_peers.argtypes = [_P, _I32, _I32, ctypes.POINTER(_P)]
-    L.mpc_episode_p2p_step.restype = ctypes.c_int
-    L.mpc_episode_p2p_step.argtypes = [
-        ctypes.POINTER(MpcEpisodeConfig), _P, ctypes.c_uint32, ctypes.c_uint32, _P, _P, _I64,
-        _I32, _I64, _I32, _P, _P, ctypes.c_size_t, _P, _P, _P, _I32, _P, _P, _I32, _P]
-    L.mpc_episode_p2p_flush.restype = ctypes.c_int
-    L.mpc_episode_p2p_flush.argtypes = [
-        ctypes.POINTER(MpcEpisodeConfig), _P, ctypes.c_uint32, _P, _P, _I64, _I32, _I64,
-        _I32, _P, ctypes.c_size_t, _P, _I32, _P, _P, _I32, _P]
-    L.mpc_episodes_state_bytes.restype = ctypes.c_size_t
-    L.mpc_episodes_state_bytes.argtypes = [_I32]
-    L.mpc_episodes_reset.restype = ctypes.c_int
-    L.mpc_episodes_reset.argtypes = [_P, _I32, _P, _P]
-    L.mpc_episodes_run.restype = ctypes.c_int
-    L.mpc_episodes_run.argtypes = [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]
-    L.mpc_fulltree_episodes_state_bytes.restype = ctypes.c_size_t
-    L.mpc_fulltree_episodes_state_bytes.argtypes = [_I32]
-    L.mpc_fulltree_episodes_reset.restype = ctypes.c_int
-    L.mpc_fulltree_episodes_reset.argtypes = [_P, _I32, _P, _P]
-    L.mpc_fulltree_episodes_run.restype = ctypes.c_int
-    L.mpc_fulltree_episodes_run.argtypes = [
-        _P, _I32, _P, _I32, _P, _I32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-        _I32, _I32, _P, _I32, _P, _P]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
+
+
+def _raises(name):
+    def errcheck(status, _fn, _args):
+        if status != 0:
+            raise MpcError(status, name)
+        return status
+    return errcheck
+
+
+def calls():
+    """The same entries for the package's own calls: a non-zero status raises
+    MpcError(status, the entry's name); size_t and string entries return theirs."""
+    global _calls
+    if _calls is None:
+        L = lib()
+        C = types.SimpleNamespace()
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = L[name]            # a function object of its own: lib()'s stays unchecked
+            fn.restype, fn.argtypes = restype, argtypes
+            if restype is c_int:
+                fn.errcheck = _raises(name)
+            setattr(C, name, fn)
+        _calls = C
+    return _calls
+
+
+def current_stream():
+    """torch's current stream as the ABI's mpc_stream_t."""
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def check(status, where):

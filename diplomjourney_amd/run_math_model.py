@@ -25,7 +25,10 @@ import numpy as np
 import torch
 
 from . import config as _cfg
-from .abi import MpcFulltreeProblem
+from .abi import (MPC_EP_ARRIVED, MPC_EP_BREAK, MPC_EP_NO_TRAJ, MpcFulltreeEpisodeConfig,
+                  MpcFulltreeProblem)
+from .device_episodes import DeviceEpisodes, DeviceFtEpisodes
+from .episode_config import tree_episode_config
 from .expansion import (Expansion, fulltree_argmin, fulltree_argmin_batched, fulltree_result,
                         fulltree_results)
 
@@ -174,14 +177,7 @@ def run_episode(seed=None, max_calls=None):
     on target, two non-moves ("Recursive error", :267-270) or `max_calls`.
     Returns (records, stop) with one (x, y, phi, v) -> result record per step."""
     global x, y, phi, v, beta
-    if seed is not None:
-        np.random.seed(seed)
-    x0 = np.random.uniform(-10, 10)
-    y0 = np.random.uniform(-10, 10)
-    phi0 = np.random.uniform(-math.pi, math.pi)
-    xt = np.random.uniform(x0 - 10, x0 + 10)
-    yt = np.random.uniform(y0 - 10, y0 + 10)
-    start_episode(x0, y0, phi0, xt, yt)
+    start_episode(*draw_starts(1, seed)[0])
     k = 0
     x_previous, y_previous = x, y
     records = []
@@ -251,7 +247,6 @@ def run_batched(starts, max_calls=None, integrator=None, chunk=256, stats=None):
     call, ret, optimal_criterion after it); raises the script's TypeError if an
     episode's first call finds no winner.  stats (optional dict) receives the
     lockstep-equivalent steps (the longest episode's calls) and the leaves."""
-    from .abi import MPC_EP_ARRIVED, MPC_EP_BREAK, MPC_EP_NO_TRAJ
     robots = [_Robot(s) for s in starts]
     cap = min(chunk, max_calls) if max_calls else chunk
     eps_dev = device_ft_episodes(starts, max_calls, integrator, cap, robots)
@@ -279,17 +274,20 @@ def run_batched(starts, max_calls=None, integrator=None, chunk=256, stats=None):
             x, y, phi, v = ret[:4]
             t = t + delta_t
             crit = g[5]
-        out.append((recs, "recursive_error" if st & MPC_EP_BREAK else
-                    "on_target" if st & MPC_EP_ARRIVED else "max_calls"))
+        out.append((recs, _stop_name(st)))
     return out
 
 
+def _stop_name(stop_bits):
+    """A device episode's stop bits as run_episode names the stop."""
+    return ("recursive_error" if stop_bits & MPC_EP_BREAK else
+            "on_target" if stop_bits & MPC_EP_ARRIVED else "max_calls")
+
+
 def device_ft_episodes(starts, max_calls=None, integrator=None, log_capacity=256, robots=None):
-    """The device state of len(starts) full-tree episodes (episode.DeviceFtEpisodes)
+    """The device state of len(starts) full-tree episodes (DeviceFtEpisodes)
     with the script's grids, constants and first incumbents: run_batched's
     engine, also driven directly by bench.py's workload G."""
-    from .abi import MpcFulltreeEpisodeConfig
-    from .episode import DeviceFtEpisodes
     eng, (vg, bg) = _device()
     integ = INTEGRATOR if integrator is None else integrator
     robots = robots or [_Robot(s) for s in starts]
@@ -413,7 +411,7 @@ def run_tree_episode(start, max_calls=None):
 def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, stats=None,
                      chunk=1024):
     """The tree-expansion episode loop for len(starts) episodes at once, one
-    robot per episode, device-resident (episode.DeviceEpisodes,
+    robot per episode, device-resident (device_episodes.DeviceEpisodes,
     mpc_episodes_run): each robot is one block that runs its episode's MPC
     steps back to back — its grid around its own (v, beta), the reference's
     enumeration, the expansion, the winner, the finishing logic m, the two-
@@ -423,9 +421,6 @@ def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, sta
     an episode's first call finds no winner).  stats (optional dict) receives
     the lockstep-equivalent steps (the longest episode's calls) and the
     candidates rolled out (each call's |V| x |B|)."""
-    import numpy as np
-    from .abi import MPC_EP_ARRIVED, MPC_EP_BREAK
-    from .episode import DeviceEpisodes, tree_episode_config
     eng = engine or _device()[0]
     R = len(starts)
     if max_calls == 0:
@@ -454,11 +449,7 @@ def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, sta
     if stats is not None:
         stats["steps"] = stats.get("steps", 0) + int(calls.max(initial=0))
         stats["candidates"] = stats.get("candidates", 0) + int(cands.sum())
-    names = []
-    for st in stop:
-        names.append("recursive_error" if st & MPC_EP_BREAK else
-                     "on_target" if st & MPC_EP_ARRIVED else "max_calls")
-    return [(records[r], names[r]) for r in range(R)]
+    return [(records[r], _stop_name(stop[r])) for r in range(R)]
 
 
 __all__ = ["configure", "shard_over", "draw_starts", "run_batched", "run_batched_lockstep",

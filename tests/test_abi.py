@@ -36,6 +36,86 @@ def test_exports_match_header(so):
         assert hasattr(so, name), name
 
 
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+            "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t}
+
+
+def _prototypes():
+    """{entry: (return type, [parameter types])} of the header's exported
+    functions, each type as its C text without the parameter's name."""
+    text = open(HEADER).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    out = {}
+    for m in re.finditer(r"([A-Za-z_][A-Za-z_0-9 ]*?[\s*]+)(mpc_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text):
+        ret, name, params = m.group(1), m.group(2), m.group(3)
+        if "static" in ret or "typedef" in ret:
+            continue
+        types_ = []
+        if params.strip() != "void":
+            for p in params.split(","):
+                # drop the parameter's name (any case: `double L`), keep `*`s.  Every
+                # parameter of the header is named; an unnamed scalar would lose its
+                # type here and fail the comparison, not pass it.
+                types_.append(re.sub(r"\b[A-Za-z_][A-Za-z_0-9]*\s*$", "", " ".join(p.split())).strip())
+        out[name] = (" ".join(ret.split()), types_)
+    return out
+
+
+def _agrees(c_type, ct):
+    """Does a ctypes type stand for this C type?"""
+    if "*" in c_type or c_type in ("mpc_stream_t", "mpc_comm_t"):
+        return (ct in (ctypes.c_void_p, ctypes.c_char_p)
+                or isinstance(ct, type) and issubclass(ct, ctypes._Pointer))
+    want = _SCALARS.get(c_type.replace("const ", ""))
+    if want is None or not (isinstance(ct, type) and issubclass(ct, ctypes._SimpleCData)) \
+            or ct in (ctypes.c_void_p, ctypes.c_char_p):
+        return False
+
+    def kind(t):                            # width, signedness, floating point
+        return ctypes.sizeof(t), t(-1).value < 0, t._type_ in "fdg"
+    return kind(ct) == kind(want)
+
+
+def test_prototypes_match_header():
+    """native.PROTOTYPES against every prototype of the header: present, the
+    same arity, and every parameter and the return value of the same kind
+    (pointer / handle, or a scalar of the same width and signedness)."""
+    protos = _prototypes()
+    assert set(protos) == _declared()
+    table = native.PROTOTYPES
+    wrong = []
+    for name, (ret, params) in sorted(protos.items()):
+        if name not in table:
+            wrong.append((name, "not in PROTOTYPES"))
+            continue
+        restype, argtypes = table[name]
+        if argtypes is None or len(argtypes) != len(params):
+            wrong.append((name, f"arity {None if argtypes is None else len(argtypes)} != {len(params)}"))
+            continue
+        if not _agrees(ret, restype):
+            wrong.append((name, f"returns {ret}, bound {restype}"))
+        for i, (c, ct) in enumerate(zip(params, argtypes)):
+            if not _agrees(c, ct):
+                wrong.append((name, f"parameter {i}: {c}, bound {ct}"))
+    assert not wrong, wrong
+    assert set(table) == set(protos)
+
+
+def test_calls_raise_with_the_entry_name():
+    """native.calls(): an int-status entry raises MpcError carrying its own
+    name and the status; the same call through native.lib() returns it."""
+    fake = ctypes.c_void_p(0x1000)
+    assert native.lib().mpc_episodes_reset(None, 1, fake, None) == abi.MPC_ERR_ARG
+    with pytest.raises(abi.MpcError) as e:
+        native.calls().mpc_episodes_reset(None, 1, fake, None)
+    assert e.value.status == abi.MPC_ERR_ARG and "mpc_episodes_reset" in str(e.value)
+    # size_t / string entries return their value, unchecked
+    assert native.calls().mpc_episodes_state_bytes(0) == 0
+    assert b"gfx950" in native.calls().mpc_version()
+
+
 def test_binding_loads():
     L = native.lib()
     assert b"gfx950" in L.mpc_version()

@@ -1244,7 +1244,7 @@ def test_overlapped_exchange_with_a_late_collective(engine):
         torch.cuda._sleep(2_000_000)          # ~1 ms on the side stream, before the collective
         return orig(out, local, group)
     try:
-        import diplomjourney_amd.episode as E
+        import diplomjourney_amd.device_episode as E
         E.gather_into = late
         torch.cuda.synchronize()
         with torch.cuda.stream(cu_reserved_stream(torch.device("cuda", 0))):

@@ -20,6 +20,8 @@ B = torch.tensor(mmt.vector_of_beta_angles(0.0), dtype=torch.float64, device="cu
 smp = eng.sample_controls_tiled if tiled else eng.sample_controls
 pool = [smp(V, B, n, ns, 500 + i) for i in range(min(K, 20))]
 L = native.lib()
+# a debug entry of the timeline build only: not in include/mpc_rollout.h, so not in
+# native.PROTOTYPES, and bound here
 L.mpc_debug_run_stats.argtypes = [ctypes.c_void_p, ctypes.c_int]
 ep = DeviceEpisode(eng, n, ns, integrator="rect+cum", log_capacity=4096, chain=True)
 buf = np.zeros((64, 8), dtype=np.uint64)
