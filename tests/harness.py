@@ -53,6 +53,7 @@ def replica_lib():
                                    "-x", "hip", "-I", os.path.join(REPO, "include")])
     L.replica_rollout.argtypes = [ctypes.POINTER(MpcProblem), _P, _P, ctypes.c_int64,
                                   ctypes.c_int32, ctypes.c_int32, _P, _P]
+    L.replica_rollout_device_consts.argtypes = L.replica_rollout.argtypes
     L.replica_set_rcp_table.argtypes = [_P, _P, ctypes.c_int64]
     L.replica_rcp_misses.restype = ctypes.c_int64
     L.replica_tan_q.argtypes = [_P, ctypes.c_int64, _P]
@@ -71,11 +72,15 @@ def device_rcp(q):
     return rd.cpu().numpy()
 
 
-def replica_rollout(problem, v_sc, b_sc, integ="rect", device_estimates=False):
+def replica_rollout(problem, v_sc, b_sc, integ="rect", device_estimates=False,
+                    device_consts=False):
     """Host replica of the kernel arithmetic -> (states [N,3,C], costs [C]).
     device_estimates: the steering tangent's reciprocal estimates come from
     the GPU (every denominator of b_sc), so the result is the device's bit for
-    bit; otherwise the host's 1.0 / q (within tolerances of it)."""
+    bit; otherwise the host's 1.0 / q (within tolerances of it).
+    device_consts: the problem constants as the device derives them (the
+    episode entries and the batched entry: consts_from_problem) instead of the
+    one-shot entries' host derivation."""
     from diplomjourney_amd.abi import INTEGRATORS
     v_sc = np.ascontiguousarray(v_sc, dtype=np.float64)
     b_sc = np.ascontiguousarray(b_sc, dtype=np.float64)
@@ -90,9 +95,9 @@ def replica_rollout(problem, v_sc, b_sc, integ="rect", device_estimates=False):
         r = device_rcp(q)
         L.replica_set_rcp_table(q.ctypes.data_as(_P), r.ctypes.data_as(_P), len(q))
     try:
-        L.replica_rollout(ctypes.byref(problem), v_sc.ctypes.data_as(_P),
-                          b_sc.ctypes.data_as(_P), n, ns, INTEGRATORS[integ],
-                          states.ctypes.data_as(_P), costs.ctypes.data_as(_P))
+        fn = L.replica_rollout_device_consts if device_consts else L.replica_rollout
+        fn(ctypes.byref(problem), v_sc.ctypes.data_as(_P), b_sc.ctypes.data_as(_P), n, ns,
+           INTEGRATORS[integ], states.ctypes.data_as(_P), costs.ctypes.data_as(_P))
         if device_estimates:
             assert L.replica_rcp_misses() == 0, "a denominator without its device estimate"
     finally:

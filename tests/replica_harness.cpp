@@ -51,9 +51,13 @@ extern "C" void replica_tan_q(const double* beta, int64_t n, double* q) {
   for (int64_t i = 0; i < n; ++i) q[i] = mpc::trig::tan_small_q(beta[i] * beta[i]);
 }
 
-extern "C" int replica_rollout(const mpc_problem_t* p, const double* v, const double* b,
-                               int64_t n_cand, int32_t n_steps, int32_t integ, double* states,
-                               double* costs) {
+// device_consts: the problem constants as the DEVICE derives them from a
+// problem (consts_from_problem, mpc_kernels.h: the episode entries and the
+// batched entry) -- squares as x * x and (s0, c0) from mpc_trig.h's sincos_fast --
+// instead of the one-shot entries' host derivation (libm pow, sin, cos).
+static int rollout_impl(const mpc_problem_t* p, const double* v, const double* b, int64_t n_cand,
+                        int32_t n_steps, int32_t integ, bool device_consts, double* states,
+                        double* costs) {
   mpc::Consts K;
   memset(&K, 0, sizeof(K));
   K.x = p->x; K.y = p->y; K.phi = p->phi;
@@ -72,6 +76,10 @@ extern "C" int replica_rollout(const mpc_problem_t* p, const double* v, const do
   double (*volatile cs)(double) = cos;
   K.s0 = sn(p->phi);
   K.c0 = cs(p->phi);
+  if (device_consts) {
+    K.inv_den = 1.0 / sqrt(K.A * K.A + K.B * K.B);
+    mpc::trig::sincos_fast(p->phi, &K.s0, &K.c0);
+  }
   const bool rot = (integ & MPC_HEADING_ROTATE) != 0;
   const bool cum = (integ & MPC_HEADING_CUMULATIVE) != 0;
   const int ig = integ & 0xff;
@@ -92,4 +100,16 @@ extern "C" int replica_rollout(const mpc_problem_t* p, const double* v, const do
     if (costs) costs[c] = cst;
   }
   return 0;
+}
+
+extern "C" int replica_rollout(const mpc_problem_t* p, const double* v, const double* b,
+                               int64_t n_cand, int32_t n_steps, int32_t integ, double* states,
+                               double* costs) {
+  return rollout_impl(p, v, b, n_cand, n_steps, integ, false, states, costs);
+}
+
+extern "C" int replica_rollout_device_consts(const mpc_problem_t* p, const double* v,
+                                             const double* b, int64_t n_cand, int32_t n_steps,
+                                             int32_t integ, double* states, double* costs) {
+  return rollout_impl(p, v, b, n_cand, n_steps, integ, true, states, costs);
 }
