@@ -22,81 +22,10 @@
 //                   with the same functions
 #pragma once
 
+#include "mpc_ftdevice.h"   // FtCtl, FtState, FtCrit, ft_crit, cost_fulltree, ft_apply
 #include "mpc_kernels.h"
 
 namespace mpc {
-
-struct FtCtl {
-  double v, beta, dphi, sd, cd;   // sd, cd = sin / cos of dphi (ROT)
-  double vh;   // v * h (RECT's position increment factor, formed once per control)
-};
-
-struct FtState {
-  double x, y, ph, s, c;
-};
-
-// The criterion's per-problem terms, folded once per problem (ft_crit) so that
-// a leaf spends 27 VALU on it instead of 35:
-//   10000*dist_target + 10*(arctan(x_t/y_t) - phi)^2 + 100*dist_line^2
-// (run_math_model.py:82-86) with dist_line = |A x - B y + C1 - C2| / hyp
-// (:53-61) evaluated as lin = fma(A, x, fma(-B, y, C1 - C2)) and
-// 100*dist_line^2 = (lin * K2) * lin, K2 = 100 / hyp^2; the sum as
-// fma(10000, dist_target, fma(lin * K2, lin, (10 a) a)).  Other roundings than
-// the script's order (a few ulps of the cost; the tests' 1e-12 bar).  The
-// line-origin sentinel (:57-58, dist_line = 1000) replaces lin by
-// S = sqrt(1e8 / K2): its term is 1e8 to within an ulp or two, and such a
-// leaf (the state AT the line origin, cost >= 1e8) never wins.
-struct FtCrit {
-  double x_t, y_t, x_0, y_0, A, nB, C, K2, S, atan_t;
-};
-
-MPC_HD __forceinline__ FtCrit ft_crit(const Consts& K, double atan_t) {
-  FtCrit F;
-  F.x_t = K.x_t;
-  F.y_t = K.y_t;
-  F.x_0 = K.x_0;
-  F.y_0 = K.y_0;
-  F.A = K.A;
-  F.nB = -K.B;
-  F.C = K.C1 - K.C2;
-  F.K2 = 100.0 * (K.inv_den * K.inv_den);
-  F.S = sqrt(1e8 / F.K2);
-  F.atan_t = atan_t;
-  return F;
-}
-
-MPC_HD __forceinline__ double cost_fulltree(double x, double y, double ph, const FtCrit& F) {
-  const double a = F.atan_t - ph;
-  const double ex = F.x_t - x, ey = F.y_t - y;
-  const double dist_target = crit_sqrt(fma(ex, ex, ey * ey));
-  const double lin0 = fma(F.A, x, fma(F.nB, y, F.C));
-  const double lin = (x == F.x_0 && y == F.y_0) ? F.S : lin0;
-  return fma(10000.0, dist_target, fma(lin * F.K2, lin, (a * 10.0) * a));
-}
-
-// iteration_of_predict (:111-115) with a precomputed control: heading first,
-// then the position with the new heading.  ROT: (s, c) rotated by the
-// control's sin / cos (the candidate rollout's complex product, 4 VALU).
-template <int INTEG, bool ROT>
-MPC_HD __forceinline__ FtState ft_apply(const FtState& in, const FtCtl& u, const Consts& K) {
-  FtState o;
-  o.ph = in.ph + u.dphi;
-  if constexpr (ROT) {
-    o.s = in.s;
-    o.c = in.c;
-    trig::rotate_sc(u.sd, u.cd, o.s, o.c);
-  } else {
-    trig::sincos_fast(o.ph, &o.s, &o.c);
-  }
-  if constexpr (INTEG == MPC_INTEG_RECT) {   // = position_step: fma(v * h, trig, p)
-    o.x = fma(u.vh, o.c, in.x);
-    o.y = fma(u.vh, o.s, in.y);
-  } else {
-    o.x = position_step<INTEG>(in.x, u.v, o.c, K);
-    o.y = position_step<INTEG>(in.y, u.v, o.s, K);
-  }
-  return o;
-}
 
 template <int INTEG>
 __global__ __launch_bounds__(kBlock) void k_ft_controls(Consts K, const double* __restrict__ V,
@@ -105,6 +34,8 @@ __global__ __launch_bounds__(kBlock) void k_ft_controls(Consts K, const double* 
                                                         uint32_t* __restrict__ no_rot) {
   const int64_t k = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (k >= s1) return;
+  // (tests/replica_harness.cpp repeats this derivation, from `FtCtl u` to the
+  // store, on the host: factored into a function, this kernel's code changed)
   FtCtl u;
   u.v = V[k / nb];
   u.beta = B[k % nb];

@@ -109,7 +109,7 @@ def saturation(value, value_mplt):
 
 def control_criterion(predicted_coordinates):
     """:82-86, host scalar (the episode's first incumbent); the leaves are
-    scored on the device by the same expression (csrc/mpc_fulltree.h)."""
+    scored on the device by the same expression (csrc/mpc_ftdevice.h)."""
     angle_from_line = (np.arctan(x_t / y_t) - predicted_coordinates[2])
     distance_from_target = get_distance_from_target(predicted_coordinates[0],
                                                     predicted_coordinates[1])

@@ -664,7 +664,9 @@ size_t mpc_fulltree_workspace_bytes(int32_t n_v, int32_t n_beta);
  * this call evaluates the shard-th of n_shards contiguous parts of the leaf
  * set (leaf indices stay global); the winner over all shards is the
  * lexicographic (cost, leaf) minimum of the shards' results (multi-GPU:
- * one all_gather of the results per MPC step). */
+ * one all_gather of the results per MPC step).  A leaf whose cost is NaN or
+ * +inf never wins; a shard (or tree) without a finite-cost leaf reports
+ * leaf -1, found 0, cost +inf and leaves k, v, beta and traj unwritten. */
 int mpc_fulltree_argmin(const mpc_fulltree_problem_t* p, const double* v_grid, int32_t n_v,
                         const double* beta_grid, int32_t n_beta, double incumbent,
                         int32_t integrator, int32_t shard, int32_t n_shards, void* ws,

@@ -15,7 +15,8 @@ def _build(name, cmd):
     out = os.path.join(BUILD, f"lib{name}.so")
     src = os.path.join(HERE, f"{name}.cpp")
     deps = [src, os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_trig.h"),
-            os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_device.h")]
+            os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_device.h"),
+            os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_ftdevice.h")]
     if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         os.makedirs(BUILD, exist_ok=True)
         subprocess.run(cmd + ["-o", out, src], check=True)
@@ -47,7 +48,7 @@ def tan_small(x):
 
 
 def replica_lib():
-    from diplomjourney_amd.abi import MpcProblem
+    from diplomjourney_amd.abi import MpcFulltreeProblem, MpcProblem
     L = _build("replica_harness", ["/opt/rocm/bin/hipcc", "-O2", "-std=c++17",
                                    "-ffp-contract=off", "-fPIC", "-shared", "--cuda-host-only",
                                    "-x", "hip", "-I", os.path.join(REPO, "include")])
@@ -57,6 +58,9 @@ def replica_lib():
     L.replica_set_rcp_table.argtypes = [_P, _P, ctypes.c_int64]
     L.replica_rcp_misses.restype = ctypes.c_int64
     L.replica_tan_q.argtypes = [_P, ctypes.c_int64, _P]
+    L.replica_fulltree.argtypes = [ctypes.POINTER(MpcFulltreeProblem), _P, ctypes.c_int32, _P,
+                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P,
+                                   ctypes.POINTER(ctypes.c_int32), _P, ctypes.c_int64, _P]
     return L
 
 
@@ -104,3 +108,51 @@ def replica_rollout(problem, v_sc, b_sc, integ="rect", device_estimates=False,
         if device_estimates:
             L.replica_set_rcp_table(None, None, 0)
     return states, costs
+
+
+def _install_device_estimates(L, beta):
+    """The device's reciprocal estimates of every tan_small denominator of beta."""
+    beta = np.unique(np.ascontiguousarray(beta, dtype=np.float64))
+    beta = beta[np.isfinite(beta)]
+    q = np.empty_like(beta)
+    L.replica_tan_q(beta.ctypes.data_as(_P), len(beta), q.ctypes.data_as(_P))
+    q = np.unique(q)
+    r = device_rcp(q)
+    L.replica_set_rcp_table(q.ctypes.data_as(_P), r.ctypes.data_as(_P), len(q))
+
+
+def replica_fulltree(problem, V, B, integ="rect", device_estimates=False, device_consts=False,
+                     leaves=()):
+    """Host replica of the full-tree arithmetic (csrc/mpc_ftdevice.h and the
+    control derivation of k_ft_controls) -> (costs [S1^3] in leaf order, no_rot,
+    layer states [len(leaves), 3, 3] of `leaves`).  problem: MpcFulltreeProblem; V, B: the grids.
+    device_consts: the batched entry's constants (the robot's by
+    consts_from_problem, the control table's from the window alone) instead of
+    the one-shot entry's host constants.  device_estimates: as replica_rollout
+    (the table's tangent is tan_fast, whose reciprocal is Newton-corrected to
+    the rounded quotient and asks for no estimate today; the table is installed
+    all the same and zero misses asserted, so that a tangent that does ask for
+    one cannot go unnoticed)."""
+    from diplomjourney_amd.abi import INTEGRATORS
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    s1 = len(V) * len(B)
+    costs = np.empty(s1 ** 3)
+    flag = ctypes.c_int32(-1)
+    L = replica_lib()
+    if device_estimates:
+        _install_device_estimates(L, B)
+    lv = np.ascontiguousarray(leaves, dtype=np.int64)
+    trajs = np.full((len(lv), 3, 3), np.nan)
+    try:
+        rc = L.replica_fulltree(ctypes.byref(problem), V.ctypes.data_as(_P), len(V),
+                                B.ctypes.data_as(_P), len(B), INTEGRATORS[integ],
+                                int(device_consts), costs.ctypes.data_as(_P), ctypes.byref(flag),
+                                lv.ctypes.data_as(_P), len(lv), trajs.ctypes.data_as(_P))
+        assert rc == 0, f"replica_fulltree: mode {integ}"
+        if device_estimates:
+            assert L.replica_rcp_misses() == 0, "a denominator without its device estimate"
+    finally:
+        if device_estimates:
+            L.replica_set_rcp_table(None, None, 0)
+    return costs, flag.value, trajs

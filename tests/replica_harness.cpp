@@ -1,7 +1,8 @@
 // Host build of the kernel's own per-candidate arithmetic (mpc_device.h:
-// step, cost, mpc_trig.h) for tests/test_replica.py.  The GPU must reproduce
-// these states and costs bit for bit: same source, same IEEE operations, fma
-// and rint are exact on both sides.  Test infrastructure only.
+// step, cost, mpc_trig.h) for tests/test_replica.py, and of the full tree's
+// per-leaf arithmetic (mpc_ftdevice.h) for tests/fulltree_cases.py.  The GPU
+// must reproduce these states and costs bit for bit: same source, same IEEE
+// operations, fma and rint are exact on both sides.  Test infrastructure only.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -55,9 +56,7 @@ extern "C" void replica_tan_q(const double* beta, int64_t n, double* q) {
 // problem (consts_from_problem, mpc_kernels.h: the episode entries and the
 // batched entry) -- squares as x * x and (s0, c0) from mpc_trig.h's sincos_fast --
 // instead of the one-shot entries' host derivation (libm pow, sin, cos).
-static int rollout_impl(const mpc_problem_t* p, const double* v, const double* b, int64_t n_cand,
-                        int32_t n_steps, int32_t integ, bool device_consts, double* states,
-                        double* costs) {
+static mpc::Consts make_consts(const mpc_problem_t* p, bool device_consts) {
   mpc::Consts K;
   memset(&K, 0, sizeof(K));
   K.x = p->x; K.y = p->y; K.phi = p->phi;
@@ -80,6 +79,13 @@ static int rollout_impl(const mpc_problem_t* p, const double* v, const double* b
     K.inv_den = 1.0 / sqrt(K.A * K.A + K.B * K.B);
     mpc::trig::sincos_fast(p->phi, &K.s0, &K.c0);
   }
+  return K;
+}
+
+static int rollout_impl(const mpc_problem_t* p, const double* v, const double* b, int64_t n_cand,
+                        int32_t n_steps, int32_t integ, bool device_consts, double* states,
+                        double* costs) {
+  const mpc::Consts K = make_consts(p, device_consts);
   const bool rot = (integ & MPC_HEADING_ROTATE) != 0;
   const bool cum = (integ & MPC_HEADING_CUMULATIVE) != 0;
   const int ig = integ & 0xff;
@@ -112,4 +118,108 @@ extern "C" int replica_rollout_device_consts(const mpc_problem_t* p, const doubl
                                              const double* b, int64_t n_cand, int32_t n_steps,
                                              int32_t integ, double* states, double* costs) {
   return rollout_impl(p, v, b, n_cand, n_steps, integ, true, states, costs);
+}
+
+// ---------------------------------------------------------------------------
+// The full tree (mpc_ftdevice.h): every leaf's cost in leaf order
+// j = (k0 * S1 + k1) * S1 + k2, by the functions the kernels run.
+#include <vector>
+
+#include "../diplomjourney_amd/csrc/mpc_ftdevice.h"
+
+template <int INTEG, bool ROT>
+static void fulltree_leaves(const mpc::Consts& K, const mpc::FtCrit& F,
+                            const std::vector<mpc::FtCtl>& ctl, double* costs,
+                            const int64_t* leaves, int64_t n_leaves, double* traj) {
+  const int64_t s1 = static_cast<int64_t>(ctl.size());
+  const mpc::FtState s0{K.x, K.y, K.phi, K.s0, K.c0};
+  if (costs) {
+    int64_t j = 0;
+    for (int64_t k0 = 0; k0 < s1; ++k0) {
+      const mpc::FtState l0 = mpc::ft_apply<INTEG, ROT>(s0, ctl[k0], K);
+      for (int64_t k1 = 0; k1 < s1; ++k1) {
+        const mpc::FtState l1 = mpc::ft_apply<INTEG, ROT>(l0, ctl[k1], K);
+        for (int64_t k2 = 0; k2 < s1; ++k2) {
+          const mpc::FtState lf = mpc::ft_apply<INTEG, ROT>(l1, ctl[k2], K);
+          costs[j++] = mpc::cost_fulltree(lf.x, lf.y, lf.ph, F);
+        }
+      }
+    }
+  }
+  for (int64_t n = 0; n < n_leaves; ++n, traj += 9) {   // k_ft_finalize's re-derivation
+    const int64_t leaf = leaves[n];
+    if (leaf < 0 || leaf >= s1 * s1 * s1) continue;
+    const int64_t kk[3] = {leaf / (s1 * s1), (leaf / s1) % s1, leaf % s1};
+    mpc::FtState st = s0;
+    for (int l = 0; l < 3; ++l) {
+      st = mpc::ft_apply<INTEG, ROT>(st, ctl[kk[l]], K);
+      traj[3 * l] = st.x;
+      traj[3 * l + 1] = st.y;
+      traj[3 * l + 2] = st.ph;
+    }
+  }
+}
+
+template <int INTEG>
+static int fulltree_impl(const mpc_fulltree_problem_t* p, const double* V, int32_t nv,
+                         const double* B, int32_t nb, bool want_rot, bool device_consts,
+                         double* costs, int32_t* no_rot, const int64_t* leaves, int64_t n_leaves,
+                         double* traj) {
+  const mpc_problem_t q{p->x, p->y, p->phi, p->x_t, p->y_t, p->x_0, p->y_0, p->L, p->t_a, p->t_b};
+  const mpc::Consts K = make_consts(&q, device_consts);
+  // the control table's constants: the one-shot entry's are the problem's; the
+  // batched entry derives window-only ones on the host (mpc_fulltree_argmin_batched)
+  mpc::Consts Kw = K;
+  if (device_consts) {
+    mpc_problem_t w = {};
+    w.x_t = 1.0;
+    w.y_t = 1.0;
+    w.L = p->L;
+    w.t_a = p->t_a;
+    w.t_b = p->t_b;
+    Kw = make_consts(&w, false);
+  }
+  const int64_t s1 = static_cast<int64_t>(nv) * nb;
+  std::vector<mpc::FtCtl> ctl(static_cast<size_t>(s1));
+  bool over = false;   // the launch-wide flag *no_rot
+  for (int64_t k = 0; k < s1; ++k) {
+    // k_ft_controls (mpc_fulltree.h), its body from `FtCtl u` to `ctl[k] = u`,
+    // with K = Kw: factored into a shared function the kernel's code changed,
+    // so the lines are repeated here
+    mpc::FtCtl u;
+    u.v = V[k / nb];
+    u.beta = B[k % nb];
+    u.vh = u.v * Kw.h;
+    const double w = Kw.L_pow2 ? u.v * Kw.inv_L : u.v / Kw.L;
+    u.dphi = mpc::heading_incr<INTEG>(w, mpc::trig::tan_fast(u.beta), Kw);
+    if (fabs(u.dphi) <= mpc::trig::kRotMax) {
+      mpc::trig::rotation_sc(u.dphi, u.sd, u.cd);
+    } else {
+      u.sd = u.cd = 0.0;
+      over = true;
+    }
+    ctl[k] = u;
+  }
+  if (no_rot) *no_rot = over ? 1 : 0;
+  const mpc::FtCrit F = mpc::ft_crit(K, p->atan_target);
+  if (want_rot && !over)   // the kernels' `ROT && *no_rot == 0u`
+    fulltree_leaves<INTEG, true>(K, F, ctl, costs, leaves, n_leaves, traj);
+  else
+    fulltree_leaves<INTEG, false>(K, F, ctl, costs, leaves, n_leaves, traj);
+  return 0;
+}
+
+// costs: S1^3 doubles or null; no_rot: the flag; traj: 9 doubles per entry of
+// `leaves`, which receive that leaf's three layer states (x, y, phi).
+extern "C" int replica_fulltree(const mpc_fulltree_problem_t* p, const double* V, int32_t nv,
+                                const double* B, int32_t nb, int32_t integ, int32_t device_consts,
+                                double* costs, int32_t* no_rot, const int64_t* leaves,
+                                int64_t n_leaves, double* traj) {
+  if (integ & MPC_HEADING_CUMULATIVE) return 1;
+  const bool rot = (integ & MPC_HEADING_ROTATE) != 0;
+  if ((integ & 0xff) == MPC_INTEG_RECT)
+    return fulltree_impl<MPC_INTEG_RECT>(p, V, nv, B, nb, rot, device_consts != 0, costs, no_rot,
+                                         leaves, n_leaves, traj);
+  return fulltree_impl<MPC_INTEG_QK21>(p, V, nv, B, nb, rot, device_consts != 0, costs, no_rot,
+                                       leaves, n_leaves, traj);
 }

@@ -1,5 +1,7 @@
 """Full-tree MPC on the GPU (mpc_fulltree_argmin, csrc/mpc_fulltree.h) against
-the CPU oracle and the reference fixtures (tests/golden/fulltree_reference.json)."""
+the CPU oracle and the reference fixtures (tests/golden/fulltree_reference.json).
+Exact winners (ties, every shard, bit for bit against a host build of the
+kernel's arithmetic): tests/test_fulltree_replica_gpu.py."""
 import json
 import math
 import os
