@@ -1,11 +1,20 @@
-// mpc_device.h — device-side arithmetic of the MPC candidate expansion (gfx950).
+// mpc_device.h — the arithmetic of the MPC candidate expansion that compiles
+// for host AND device (gfx950): the kernels run it, and the host replica
+// (tests/replica_harness.cpp) calls the same functions.
+//
+//   Consts, consts_from_problem     per-problem constants, as the device derives them
+//   quad_const, heading_incr, position_step, step_core, step_start, cum_pose,
+//   step_safe, crit_sqrt, cost      one step and the criterion
+//   Circle .. ObsTable, NoObs, CircleObs   keep-out circles: tables and lane hooks
+//   rollout_candidate_l, rollout_candidate  one candidate as the kernels evaluate it
 //
 // Every function here states one piece of ShittyWizard/DiplomJourney's
 // math_model_tree.py in IEEE fp64 with the reference's operation order.  The
 // translation unit is compiled with -ffp-contract=off so each + - * / is one
 // rounding, exactly as in CPython; tan/sincos/sqrt are the ROCm device
 // kernel's own fp64 routines (mpc_trig.h; faithfully rounded, <= 1 ulp from
-// glibc's).
+// glibc's).  Nothing here is device-only: reductions, keys and the sampler's
+// hash are in mpc_argmin.h and mpc_sampler.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -31,6 +40,35 @@ struct Consts {
   int32_t L_pow2;          // v/L == v*inv_L exactly
   int32_t pad_;
 };
+
+// Problem constants derived on the device (batched robots, episode).  The
+// squares are x*x (glibc pow(x, 2.0) differs by 1 ulp in ~0.1% of inputs);
+// the single-problem host path derives them with libm pow.
+MPC_HD __forceinline__ Consts consts_from_problem(const mpc_problem_t& p) {
+  Consts K;
+  K.x = p.x;
+  K.y = p.y;
+  K.phi = p.phi;
+  K.x_t = p.x_t;
+  K.y_t = p.y_t;
+  K.x_0 = p.x_0;
+  K.y_0 = p.y_0;
+  K.A = p.y_t - p.y_0;
+  K.B = p.x_t - p.x_0;
+  K.C1 = p.x_t * p.y_0;
+  K.C2 = p.y_t * p.x_0;
+  K.inv_den = 1.0 / sqrt(K.A * K.A + K.B * K.B);
+  K.L = p.L;
+  int e;
+  const double m = frexp(p.L, &e);
+  K.L_pow2 = (m == 0.5) ? 1 : 0;
+  K.inv_L = K.L_pow2 ? 1.0 / p.L : 0.0;
+  K.h = p.t_b - p.t_a;
+  K.hlgth = 0.5 * (p.t_b - p.t_a);
+  trig::sincos_fast(p.phi, &K.s0, &K.c0);
+  K.pad_ = 0;
+  return K;
+}
 
 // QUADPACK dqk21 Kronrod weights wgk(1..11).
 constexpr double kWGK[11] = {
@@ -362,120 +400,6 @@ MPC_HD inline double rollout_candidate(const Consts& K, const double* v, const d
                                        int64_t ld, int64_t col, int n_steps, double* traj) {
   return K.L_pow2 ? rollout_candidate_l<INTEG, ROT, true>(K, v, b, ld, col, n_steps, traj)
                   : rollout_candidate_l<INTEG, ROT, false>(K, v, b, ld, col, n_steps, traj);
-}
-
-// Total order on costs for the arg-min: non-finite costs (NaN, +inf) map to
-// the largest key and never win; -0 is folded into +0.
-__device__ __forceinline__ uint64_t cost_key(double c) {
-  if (!(c < __builtin_inf())) return ~0ull;
-  c = c + 0.0;
-  const uint64_t u = static_cast<uint64_t>(__double_as_longlong(c));
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-// cost_key for a criterion value, which is never negative (a sum of
-// 10000 * sqrt(.) and squares: +0 at least, or NaN / +inf): the same key
-// without the sign fold — 2 VALU per candidate instead of ~6.
-__device__ __forceinline__ uint64_t cost_key_nonneg(double c) {
-  const uint64_t u = static_cast<uint64_t>(__double_as_longlong(c));
-  return c < __builtin_inf() ? (u | 0x8000000000000000ull) : ~0ull;
-}
-
-__device__ __forceinline__ double key_cost(uint64_t k) {
-  if (k == ~0ull) return __builtin_inf();
-  const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double(static_cast<long long>(u));
-}
-
-// Lexicographic (key, index) order: lowest cost, then lowest index — the
-// first strict minimum of the reference's ascending scan (:351).
-__device__ __forceinline__ bool rec_less(uint64_t ka, int64_t ia, uint64_t kb, int64_t ib) {
-  return ka < kb || (ka == kb && ia < ib);
-}
-
-// One level of the wave reduction: every lane combines its (key, index) with
-// the lane the DPP pattern CTRL names.  DPP moves run on the VALU: a level is
-// a few cycles instead of an LDS round trip per 32-bit half (ds_bpermute).
-// Lanes of rows outside RM receive an undefined value (no copy of the old
-// one): the reduction below reads only lane 63, whose inputs are all defined.
-template <int CTRL, int RM = 0xf>
-__device__ __forceinline__ void argmin_dpp_level(uint64_t& k, int64_t& i) {
-  auto mv = [](uint64_t x) {
-    const int lo = __builtin_amdgcn_mov_dpp(static_cast<int>(x), CTRL, RM, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp(static_cast<int>(x >> 32), CTRL, RM, 0xf, true);
-    return (static_cast<uint64_t>(static_cast<uint32_t>(hi)) << 32) | static_cast<uint32_t>(lo);
-  };
-  const uint64_t ok = mv(k);
-  const int64_t oi = static_cast<int64_t>(mv(static_cast<uint64_t>(i)));
-  const bool lt = rec_less(ok, oi, k, i);
-  k = lt ? ok : k;
-  i = lt ? oi : i;
-}
-
-// Lexicographic (key, index) minimum over the 64 lanes of a wave (all lanes
-// active), returned in every lane.  quad_perm [1,0,3,2] and [2,3,0,1], then
-// row_half_mirror and row_mirror leave each row of 16 lanes holding its
-// minimum in every lane; row_bcast:15 (into rows 1, 3: lane 31 then holds
-// rows 0-1, lane 63 rows 2-3) and row_bcast:31 (lane 31 into row 3) fold the
-// rows into lane 63, which is broadcast.  The minimum of a total order does
-// not depend on the combination order: the same result as any other
-// reduction tree.
-__device__ __forceinline__ void wave_argmin(uint64_t& k, int64_t& i) {
-  argmin_dpp_level<0xB1>(k, i);
-  argmin_dpp_level<0x4E>(k, i);
-  argmin_dpp_level<0x141>(k, i);
-  argmin_dpp_level<0x140>(k, i);
-  argmin_dpp_level<0x142, 0xA>(k, i);
-  argmin_dpp_level<0x143, 0xC>(k, i);
-  auto lane63 = [](uint64_t x) {
-    const uint32_t lo = __builtin_amdgcn_readlane(static_cast<int>(x), 63);
-    const uint32_t hi = __builtin_amdgcn_readlane(static_cast<int>(x >> 32), 63);
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-  };
-  k = lane63(k);
-  i = static_cast<int64_t>(lane63(static_cast<uint64_t>(i)));
-}
-
-// Minimum of a 32-bit value over the 64 lanes of a wave (all lanes active),
-// returned in every lane: the DPP pattern of wave_argmin with v_min_u32
-// (lanes a pattern does not feed get the identity 0xffffffff).
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
-  auto lvl = [](uint32_t v, auto ctrl, auto rm) {
-    constexpr int C = decltype(ctrl)::value, M = decltype(rm)::value;
-    const uint32_t o = static_cast<uint32_t>(
-        __builtin_amdgcn_update_dpp(-1, static_cast<int>(v), C, M, 0xf, false));
-    return v < o ? v : o;
-  };
-  using std::integral_constant;
-  x = lvl(x, integral_constant<int, 0xB1>{}, integral_constant<int, 0xf>{});
-  x = lvl(x, integral_constant<int, 0x4E>{}, integral_constant<int, 0xf>{});
-  x = lvl(x, integral_constant<int, 0x141>{}, integral_constant<int, 0xf>{});
-  x = lvl(x, integral_constant<int, 0x140>{}, integral_constant<int, 0xf>{});
-  x = lvl(x, integral_constant<int, 0x142>{}, integral_constant<int, 0xA>{});
-  x = lvl(x, integral_constant<int, 0x143>{}, integral_constant<int, 0xC>{});
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), 63));
-}
-
-// wave_argmin for 31-bit indices (a lane without a candidate holds the
-// sentinel (~0, INT64_MAX)): three 32-bit minima — the key's high word, its
-// low word among the lanes holding that high word, the index among the lanes
-// holding the whole key — give the same lexicographic minimum with ~40 VALU
-// instead of ~70 (two 64-bit compares and four selects per level).
-__device__ __forceinline__ void wave_argmin32(uint64_t& k, int64_t& i) {
-  const uint32_t hi = static_cast<uint32_t>(k >> 32), lo = static_cast<uint32_t>(k);
-  const uint32_t ix = k == ~0ull ? 0xffffffffu : static_cast<uint32_t>(i);
-  const uint32_t m1 = wave_min_u32(hi);
-  const uint32_t m2 = wave_min_u32(hi == m1 ? lo : 0xffffffffu);
-  const uint32_t m3 = wave_min_u32(hi == m1 && lo == m2 ? ix : 0xffffffffu);
-  k = (static_cast<uint64_t>(m1) << 32) | m2;
-  i = k == ~0ull ? INT64_MAX : static_cast<int64_t>(m3);
-}
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
 }
 
 }  // namespace mpc

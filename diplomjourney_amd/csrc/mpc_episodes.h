@@ -29,7 +29,12 @@
 // (stop_rule 0, the operator schedule) can share one launch.
 #pragma once
 
+#include "mpc_argmin.h"
+#include "mpc_device.h"
 #include "mpc_episode.h"
+#include "mpc_generated.h"
+#include "mpc_lanes.h"
+#include "mpc_winner.h"
 
 namespace mpc {
 

@@ -43,8 +43,10 @@
 // host-built mpc_fulltree_episode_config_t by mpc_fulltree_episodes_reset).
 #pragma once
 
+#include "mpc_argmin.h"
 #include "mpc_episodes.h"
 #include "mpc_fulltree.h"
+#include "mpc_lanes.h"
 
 namespace mpc {
 

@@ -22,8 +22,9 @@
 //                   with the same functions
 #pragma once
 
+#include "mpc_argmin.h"
 #include "mpc_ftdevice.h"   // FtCtl, FtState, FtCrit, ft_crit, cost_fulltree, ft_apply
-#include "mpc_kernels.h"
+#include "mpc_lanes.h"
 
 namespace mpc {
 

@@ -1,7 +1,9 @@
 // mpc_rollout.hip — C ABI (include/mpc_rollout.h) over the MI355X kernels of
 // the MPC candidate expansion (ShittyWizard/DiplomJourney
-// math_model_tree.py:278-362).  Kernels: mpc_kernels.h (rollout, arg-min,
-// selection, sampler) and mpc_episode.h (device-resident episode).
+// math_model_tree.py:278-362).  Kernels: mpc_kernels.h (rollout + arg-min,
+// selection), mpc_finalize.h, mpc_sampler.h, and the device-resident episode's
+// (mpc_episode.h, mpc_generated.h, mpc_exchange.h, mpc_chain.h, mpc_run.h);
+// the host's problem constants: mpc_host_consts.h.
 //
 // HBM traffic of k_rollout_argmin: 16 B per candidate-step read once
 // (v, beta fp64 SoA), 16 B per block written.  See DESIGN.md for the roofline.
@@ -17,55 +19,26 @@
 #include <type_traits>
 
 #include "../../include/mpc_rollout.h"
+#include "mpc_argmin.h"
+#include "mpc_chain.h"
 #include "mpc_comm.h"
+#include "mpc_device.h"
 #include "mpc_episode.h"
-#include "mpc_ftepisodes.h"
 #include "mpc_episodes.h"
+#include "mpc_exchange.h"
+#include "mpc_finalize.h"
+#include "mpc_ftepisodes.h"
 #include "mpc_fulltree.h"
+#include "mpc_generated.h"
+#include "mpc_host_consts.h"
 #include "mpc_kernels.h"
+#include "mpc_lanes.h"
 #include "mpc_run.h"
+#include "mpc_sampler.h"
+#include "mpc_winner.h"
 
 namespace mpc {
 namespace {
-
-// libm through volatile pointers: the compiler must not fold pow(x, 2.0) into
-// x*x (Python's `a ** 2` is libm pow, which is not always x*x).
-double (*volatile g_libm_pow)(double, double) = pow;
-double (*volatile g_libm_sin)(double) = sin;
-double (*volatile g_libm_cos)(double) = cos;
-
-// The wheelbase is a power of two: sums scaled by 1/L are then exact, which the
-// PL2 kernel instantiations and Consts::L_pow2 (consts_from_problem) rely on.
-inline bool length_pow2(double L) {
-  int e;
-  return frexp(L, &e) == 0.5;
-}
-
-// Problem constants derived on the host with the reference's libm calls.
-Consts host_consts(const mpc_problem_t& p) {
-  Consts K;
-  memset(&K, 0, sizeof(K));
-  K.x = p.x;
-  K.y = p.y;
-  K.phi = p.phi;
-  K.x_t = p.x_t;
-  K.y_t = p.y_t;
-  K.x_0 = p.x_0;
-  K.y_0 = p.y_0;
-  K.A = p.y_t - p.y_0;
-  K.B = p.x_t - p.x_0;
-  K.C1 = p.x_t * p.y_0;
-  K.C2 = p.y_t * p.x_0;
-  K.inv_den = 1.0 / sqrt(g_libm_pow(K.A, 2.0) + g_libm_pow(K.B, 2.0));
-  K.L = p.L;
-  K.L_pow2 = length_pow2(p.L) ? 1 : 0;
-  K.inv_L = K.L_pow2 ? 1.0 / p.L : 0.0;
-  K.h = p.t_b - p.t_a;
-  K.hlgth = 0.5 * (p.t_b - p.t_a);
-  K.s0 = g_libm_sin(p.phi);
-  K.c0 = g_libm_cos(p.phi);
-  return K;
-}
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -158,7 +131,7 @@ int64_t device_cus() {
 }
 
 // The bounded device waits count wall_clock64 ticks at kWallHz
-// (mpc_episode.h).  A device whose constant-rate clock runs at another rate
+// (mpc_exchange.h).  A device whose constant-rate clock runs at another rate
 // would scale every budget silently: the entries with such waits refuse it.
 // Unknown (no device / the query fails): not refused here (the launch reports).
 bool wall_clock_ok() {
@@ -1451,13 +1424,7 @@ int mpc_fulltree_argmin_batched(const mpc_fulltree_problem_t* problems,
   if (mode_ok(integrator, false) != MPC_OK) return MPC_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < mpc_fulltree_batched_workspace_bytes(n_problems, n_v, n_beta))
     return MPC_ERR_WORKSPACE;
-  mpc_problem_t q = {};
-  q.x_t = 1.0;   // window-only constants for the shared control table
-  q.y_t = 1.0;
-  q.L = L;
-  q.t_a = t_a;
-  q.t_b = t_b;
-  const Consts Kw = host_consts(q);
+  const Consts Kw = host_window_consts(L, t_a, t_b);   // the shared control table's
   char* w = static_cast<char*>(ws);
   FtCtl* ctl = reinterpret_cast<FtCtl*>(w);
   uint32_t* no_rot = reinterpret_cast<uint32_t*>(w + ft_flag_offset(s1));

@@ -42,7 +42,13 @@
 // (graph replays repeat their epochs safely).
 #pragma once
 
+#include "mpc_argmin.h"
+#include "mpc_chain.h"
 #include "mpc_episode.h"
+#include "mpc_exchange.h"
+#include "mpc_finalize.h"
+#include "mpc_lanes.h"
+#include "mpc_winner.h"
 
 namespace mpc {
 
@@ -143,7 +149,7 @@ __device__ bool run_poll_records(const Rec* __restrict__ p, Rec* __restrict__ z,
 }
 
 // Tile blocks: claim units in order and run the chained step's tile body on
-// each (chain_tiles, mpc_episode.h, for one tile of step j with epoch e0 + j).
+// each (chain_tiles, mpc_chain.h, for one tile of step j with epoch e0 + j).
 template <bool PL2, bool TILED>
 __device__ __forceinline__ void run_tiles(EpisodeState* __restrict__ S, uint32_t e0,
                                           RunCtlPtr ctl, int K, int64_t n_cand, int n_steps,

@@ -258,7 +258,7 @@ class DeviceEpisode:
         self.log = torch.zeros(self.log_capacity * LOG_BYTES, dtype=torch.uint8, device=dev)
         self._log_host = None             # pinned copy of the log (read_log)
         # zeroed: an exchange step's tagged block records must never find an
-        # old allocation's bytes carrying a tag (mpc_episode.h store_tagged_rec)
+        # old allocation's bytes carrying a tag (mpc_exchange.h store_tagged_rec)
         self.ws = torch.zeros(self.lib.mpc_workspace_bytes(self.n_local, self.n_steps),
                               dtype=torch.uint8, device=dev)
         self._integ = INTEGRATORS[integrator]

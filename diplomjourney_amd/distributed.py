@@ -12,7 +12,7 @@ semantically the north star's all-reduce(min+index):
     chain=True), the bench's N > 1 path): `gather_bytes` of each rank's
     536-byte mpc_candidate_t (cost, global index, the candidate's N
     controls); the NEXT launch's block 0 selects the winner and re-rolls it
-    from the gathered controls (mpc_episode.h advance_from_candidates);
+    from the gathered controls (mpc_exchange.h advance_from_candidates);
   * the generic per-call path (Episode, the drop-in's shards):
     `exchange_winner` = all_gather of the 808-byte mpc_result_t records
     (winner trajectory included) + k_select_winner.
@@ -43,7 +43,7 @@ def gather_results(local_out, group=None):
 
 
 def _key(res):
-    """Total order used on device (mpc_device.h cost_key): non-finite or
+    """Total order used on device (mpc_argmin.h cost_key): non-finite or
     missing winners last, then cost, then global index."""
     if res.index < 0 or not (res.cost < math.inf):
         return (1, 0.0, 0)

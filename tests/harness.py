@@ -1,5 +1,6 @@
 """Builds and loads the host test harnesses (trig_harness.cpp, replica_harness.cpp)."""
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -11,12 +12,16 @@ BUILD = os.path.join(REPO, "oracle", "_build")
 _P = ctypes.c_void_p
 
 
+def library_headers():
+    """Every header a harness may include: the library's csrc/*.h and the ABI header."""
+    return sorted(glob.glob(os.path.join(REPO, "diplomjourney_amd", "csrc", "*.h"))) + [
+        os.path.join(REPO, "include", "mpc_rollout.h")]
+
+
 def _build(name, cmd):
     out = os.path.join(BUILD, f"lib{name}.so")
     src = os.path.join(HERE, f"{name}.cpp")
-    deps = [src, os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_trig.h"),
-            os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_device.h"),
-            os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_ftdevice.h")]
+    deps = [src, *library_headers()]
     if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         os.makedirs(BUILD, exist_ok=True)
         subprocess.run(cmd + ["-o", out, src], check=True)

@@ -1,8 +1,12 @@
 // Host build of the kernel's own per-candidate arithmetic (mpc_device.h:
-// step, cost, mpc_trig.h) for tests/test_replica.py, and of the full tree's
-// per-leaf arithmetic (mpc_ftdevice.h) for tests/fulltree_cases.py.  The GPU
-// must reproduce these states and costs bit for bit: same source, same IEEE
-// operations, fma and rint are exact on both sides.  Test infrastructure only.
+// problem constants, step, cost; mpc_trig.h) for tests/test_replica.py, and of
+// the full tree's per-leaf arithmetic (mpc_ftdevice.h) for
+// tests/fulltree_cases.py.  The GPU must reproduce these states and costs bit
+// for bit: same source, same IEEE operations, fma and rint are exact on both
+// sides.  The host-derived constants are the library's too
+// (mpc_host_consts.h).  One body is repeated here, not shared: the
+// per-control lines of k_ft_controls (mpc_fulltree.h), marked below -- as a
+// shared function they changed the kernel's code.  Test infrastructure only.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -10,6 +14,7 @@
 #include <unordered_map>
 
 #include "../diplomjourney_amd/csrc/mpc_device.h"
+#include "../diplomjourney_amd/csrc/mpc_host_consts.h"
 
 // The device's reciprocal estimates (v_rcp_f64 is not an IEEE operation):
 // a GPU test fetches them for every denominator the rollout will form
@@ -53,39 +58,17 @@ extern "C" void replica_tan_q(const double* beta, int64_t n, double* q) {
 }
 
 // device_consts: the problem constants as the DEVICE derives them from a
-// problem (consts_from_problem, mpc_kernels.h: the episode entries and the
-// batched entry) -- squares as x * x and (s0, c0) from mpc_trig.h's sincos_fast --
-// instead of the one-shot entries' host derivation (libm pow, sin, cos).
-static mpc::Consts make_consts(const mpc_problem_t* p, bool device_consts) {
-  mpc::Consts K;
-  memset(&K, 0, sizeof(K));
-  K.x = p->x; K.y = p->y; K.phi = p->phi;
-  K.x_t = p->x_t; K.y_t = p->y_t; K.x_0 = p->x_0; K.y_0 = p->y_0;
-  K.A = p->y_t - p->y_0; K.B = p->x_t - p->x_0;
-  K.C1 = p->x_t * p->y_0; K.C2 = p->y_t * p->x_0;
-  double (*volatile pw)(double, double) = pow;
-  K.inv_den = 1.0 / sqrt(pw(K.A, 2.0) + pw(K.B, 2.0));
-  K.L = p->L;
-  int e;
-  K.L_pow2 = frexp(p->L, &e) == 0.5;
-  K.inv_L = K.L_pow2 ? 1.0 / p->L : 0.0;
-  K.h = p->t_b - p->t_a;
-  K.hlgth = 0.5 * (p->t_b - p->t_a);
-  double (*volatile sn)(double) = sin;
-  double (*volatile cs)(double) = cos;
-  K.s0 = sn(p->phi);
-  K.c0 = cs(p->phi);
-  if (device_consts) {
-    K.inv_den = 1.0 / sqrt(K.A * K.A + K.B * K.B);
-    mpc::trig::sincos_fast(p->phi, &K.s0, &K.c0);
-  }
-  return K;
+// problem (consts_from_problem, mpc_device.h: the episode entries and the
+// batched entry) instead of the one-shot entries' host derivation
+// (host_consts, mpc_host_consts.h).  Both are the library's own functions.
+static mpc::Consts problem_consts(const mpc_problem_t& p, bool device_consts) {
+  return device_consts ? mpc::consts_from_problem(p) : mpc::host_consts(p);
 }
 
 static int rollout_impl(const mpc_problem_t* p, const double* v, const double* b, int64_t n_cand,
                         int32_t n_steps, int32_t integ, bool device_consts, double* states,
                         double* costs) {
-  const mpc::Consts K = make_consts(p, device_consts);
+  const mpc::Consts K = problem_consts(*p, device_consts);
   const bool rot = (integ & MPC_HEADING_ROTATE) != 0;
   const bool cum = (integ & MPC_HEADING_CUMULATIVE) != 0;
   const int ig = integ & 0xff;
@@ -166,19 +149,10 @@ static int fulltree_impl(const mpc_fulltree_problem_t* p, const double* V, int32
                          double* costs, int32_t* no_rot, const int64_t* leaves, int64_t n_leaves,
                          double* traj) {
   const mpc_problem_t q{p->x, p->y, p->phi, p->x_t, p->y_t, p->x_0, p->y_0, p->L, p->t_a, p->t_b};
-  const mpc::Consts K = make_consts(&q, device_consts);
+  const mpc::Consts K = problem_consts(q, device_consts);
   // the control table's constants: the one-shot entry's are the problem's; the
   // batched entry derives window-only ones on the host (mpc_fulltree_argmin_batched)
-  mpc::Consts Kw = K;
-  if (device_consts) {
-    mpc_problem_t w = {};
-    w.x_t = 1.0;
-    w.y_t = 1.0;
-    w.L = p->L;
-    w.t_a = p->t_a;
-    w.t_b = p->t_b;
-    Kw = make_consts(&w, false);
-  }
+  const mpc::Consts Kw = device_consts ? mpc::host_window_consts(p->L, p->t_a, p->t_b) : K;
   const int64_t s1 = static_cast<int64_t>(nv) * nb;
   std::vector<mpc::FtCtl> ctl(static_cast<size_t>(s1));
   bool over = false;   // the launch-wide flag *no_rot

@@ -13,7 +13,8 @@
 // and prints a 64-bit FNV-1a checksum of every output byte, so that the test
 // can compare a plain and an -fsanitize=address,undefined build bit for bit.
 // The restated reference code lives in mpc_oracle.c (math_model_tree.py:56-115,
-// run_math_model.py:82-197) and mpc_device.h; nothing here restates it.
+// run_math_model.py:82-197) and mpc_device.h (the host-derived constants:
+// mpc_host_consts.h); nothing here restates it.
 #include <stdio.h>
 #include <stdlib.h>
 

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from conftest import call_controls, call_problem
+from harness import library_headers
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -35,10 +36,9 @@ def _build(mode):
     os.makedirs(BUILD, exist_ok=True)
     exe = os.path.join(BUILD, f"driver_{mode}")
     srcs = [os.path.join(REPO, "oracle", "mpc_oracle.c"), os.path.join(HERE, "sanitize_driver.cpp"),
-            os.path.join(HERE, "replica_harness.cpp"),
-            os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_device.h"),
-            os.path.join(REPO, "diplomjourney_amd", "csrc", "mpc_trig.h")]
-    if os.path.exists(exe) and all(os.path.getmtime(s) < os.path.getmtime(exe) for s in srcs):
+            os.path.join(HERE, "replica_harness.cpp")]
+    deps = srcs + library_headers()
+    if os.path.exists(exe) and all(os.path.getmtime(s) < os.path.getmtime(exe) for s in deps):
         return exe
     obj = os.path.join(BUILD, f"oracle_{mode}.o")
     san = SAN if mode == "san" else []

@@ -52,7 +52,7 @@ def build():
     cs = os.path.join(d, "diplomjourney_amd", "csrc")
     st = lambda slot: STAMP.format(slot=slot)   # noqa: E731
     b0 = lambda q: f"if (blockIdx.x == 0 && threadIdx.x == 0) {st(B0_BASE + q)};"   # noqa: E731
-    patch(os.path.join(cs, "mpc_kernels.h"), [
+    patch(os.path.join(cs, "mpc_finalize.h"), [
         ("                             __HIP_MEMORY_SCOPE_WORKGROUP);\n      }\n      if (early_on && q >= 192",
          "                             __HIP_MEMORY_SCOPE_WORKGROUP);\n"
          f"        if (blockIdx.x == 0 && q == 64) {STAMP.format(slot=B0_BASE + 18)};\n"
@@ -61,12 +61,16 @@ def build():
          "      __hip_atomic_store(&s_pose, ok ? 1 : 2, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);\n"
          f"      if (blockIdx.x == 0) {STAMP.format(slot=B0_BASE + 19)};\n"),
     ])
-    patch(os.path.join(cs, "mpc_kernels.h"), [
+    patch(os.path.join(cs, "mpc_winner.h"), [
         ("  __syncthreads();\n  key = s_key;\n", f"  __syncthreads();\n  {b0(16)}\n  key = s_key;\n"),
         ("  side_a();\n", f"  {b0(17)}\n  side_a();\n"),
+        ("  __syncthreads();\n  // Regular rotation-mode winner",
+         f"  __syncthreads();\n  {b0(4)}\n  // Regular rotation-mode winner"),
     ])
-    patch(os.path.join(cs, "mpc_kernels.h"), [
+    patch(os.path.join(cs, "mpc_argmin.h"), [
         ("struct Rec {\n", f"__device__ uint64_t g_tl[8 * {NB} + 32];\n\nstruct Rec {{\n"),
+    ])
+    patch(os.path.join(cs, "mpc_finalize.h"), [
         ("  if (stage) s_head[threadIdx.x - 64] = head_word;\n",
          f"  {b0(1)}\n"
          "  if (stage) s_head[threadIdx.x - 64] = head_word;\n"),
@@ -88,15 +92,13 @@ def build():
         ("                 hook.chain_pub, hook.chain_pub_words, hook.publish_epoch, early, s_pub);\n",
          "                 hook.chain_pub, hook.chain_pub_words, hook.publish_epoch, early, s_pub);\n"
          f"    {b0(8)}\n"),
-        ("  __syncthreads();\n  // Regular rotation-mode winner",
-         f"  __syncthreads();\n  {b0(4)}\n  // Regular rotation-mode winner"),
     ])
     t = lambda q: f"if (threadIdx.x == 0) {STAMP.format(slot=f'8 * blockIdx.x + {q}')};"   # noqa: E731
-    patch(os.path.join(cs, "mpc_episode.h"), [
+    patch(os.path.join(cs, "mpc_chain.h"), [
         ("  block_argmin<true>(best_k, best_i);   // (indices < n_cand < 2^31)\n",
          f"  {t(4)}\n  block_argmin<true>(best_k, best_i);   // (indices < n_cand < 2^31)\n  {t(5)}\n"),
     ])
-    patch(os.path.join(cs, "mpc_episode.h"), [
+    patch(os.path.join(cs, "mpc_exchange.h"), [
         # P2P block 0 (p2p_complete): candidate from the records, posted, the
         # world's gathered; published (advance_from_candidates' store_update)
         ("                           lc);\n  if (static_cast<int>(threadIdx.x) < world)",
@@ -108,6 +110,8 @@ def build():
          f"  {b0(3)}\n"),
         ("               kPubWords, publish_epoch);\n  emit_winner_tail",
          f"               kPubWords, publish_epoch);\n  {b0(8)}\n  emit_winner_tail"),
+    ])
+    patch(os.path.join(cs, "mpc_episode.h"), [   # episode_advance
         ("  EpisodeHead* S = &H;\n  S->steps_for_slowing -= 1;\n",
          f"  {b0(9)}\n  EpisodeHead* S = &H;\n  S->steps_for_slowing -= 1;\n"),
         ("  const double x_prev = S->x, y_prev = S->y;   // x_previous",
@@ -117,6 +121,8 @@ def build():
          f"  }} else {{\n    episode_prepare(c, *S);\n  }}\n  {b0(12)}\n}}\n"),
         ("  L.status = status;\n  if (ended) {\n",
          f"  L.status = status;\n  {b0(6)}\n  if (ended) {{\n"),
+    ])
+    patch(os.path.join(cs, "mpc_chain.h"), [     # k_episode_chain, chain_tiles
         ("  if (blockIdx.x == 0) {\n    if (has_prev) {\n",
          f"  if (blockIdx.x == 0) {{\n    {t(0)}\n    if (has_prev) {{\n"),
         ("  constexpr int CPL = 2;\n  __shared__ __attribute__((aligned(16))) uint32_t s_w[kPubWords];\n",

@@ -16,7 +16,9 @@
 #include <algorithm>
 #include <vector>
 
-#include "mpc_kernels.h"
+#include "mpc_argmin.h"    // Rec, block_argmin
+#include "mpc_kernels.h"   // kStreamWaves
+#include "mpc_lanes.h"     // rollout_lane_glds_k
 
 #define CHECK(x)                                                                    \
   do {                                                                              \

@@ -1,4 +1,4 @@
-// Probe: the rates of wall_clock64() (the bounded waits' clock, mpc_episode.h)
+// Probe: the rates of wall_clock64() (the bounded waits' clock, mpc_exchange.h)
 // and clock64() (torch.cuda._sleep's) on this GPU, against HIP events.
 //   hipcc --offload-arch=gfx950 -O2 -o tools/micro/wallclock tools/micro/wallclock.hip
 #include <hip/hip_runtime.h>
