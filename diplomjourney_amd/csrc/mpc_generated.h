@@ -81,8 +81,10 @@ __global__ __launch_bounds__(kBlock) void k_episode_sample(
   const int nv = s_nv, nb = s_nb;
   const uint64_t seed = S->h.seed;
   const uint32_t n_grid = static_cast<uint32_t>(nv) * static_cast<uint32_t>(nb);
-  for (uint32_t k = threadIdx.x; k < n_grid; k += kBlock)  // nv, nb <= 64: fits in LDS
-    s_grid[k] = make_double2(s_v[k / nb], s_b[k % nb]);
+  const bool staged = n_grid <= static_cast<uint32_t>(kSampleLdsEntries);
+  if (staged)
+    for (uint32_t k = threadIdx.x; k < n_grid; k += kBlock)
+      s_grid[k] = make_double2(s_v[k / nb], s_b[k % nb]);
   __syncthreads();
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     S->h.nv = nv;
@@ -91,6 +93,22 @@ __global__ __launch_bounds__(kBlock) void k_episode_sample(
     for (int i = 0; i < nb; ++i) S->grid_b[i] = s_b[i];
   }
   if (n_grid == 0 && !c.enumerate) return;
+  if (!staged) {
+    // more than kSampleLdsEntries of the 64 x 64 entries (grids far wider than
+    // the reference's): direct lookups in s_v / s_b, one division per element,
+    // as k_sample_controls does for such a grid
+    for (int64_t cc = blockIdx.x * static_cast<int64_t>(kBlock) + threadIdx.x; cc < n_cand;
+         cc += static_cast<int64_t>(gridDim.x) * kBlock) {
+      const uint64_t g = static_cast<uint64_t>(base + cc);
+      for (int st = 0; st < n_steps; ++st) {
+        const bool pad = c.enumerate && g >= n_grid;
+        const uint32_t k = pad ? 0u : grid_entry(seed, st, g, n_grid, 1);
+        v[ctl_off<false>(st, cc, n_cand)] = pad ? __builtin_nan("") : s_v[k / nb];
+        b[ctl_off<false>(st, cc, n_cand)] = pad ? 0.0 : s_b[k % nb];
+      }
+    }
+    return;
+  }
   sample_items(s_grid, n_grid, n_cand, n_steps, seed, base, c.enumerate ? 2 : 1, v, b, n_cand,
                pairs);
 }

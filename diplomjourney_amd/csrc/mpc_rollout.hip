@@ -695,17 +695,35 @@ int mpc_episode_generate_step(const mpc_episode_config_t* cfg, void* state, int6
   double* part_v = reinterpret_cast<double*>(w + gen_ctl_offset(n_cand));
   double* part_b = part_v + grid * MPC_MAX_STEPS;
   const EpisodeHook hook = episode_hook(S, true, log, log_capacity);
+  bool launched = true;
   dispatch_mode(integrator, [&](auto I, auto R) {
     dispatch_bools(
         [&](auto PL2) {
-          k_rollout_generated<I, R, PL2><<<grid, kBlock, lds, st>>>(
-              *cfg, S, n_cand, n_steps, index_base, part, part_v, part_b);
+          // a grid near the 64 x 64 bound: with the kernel's static LDS more
+          // than the 64 KiB a launch gets unasked, so the kernel opts in
+          if (lds > 48 * 1024)
+            launched = hipFuncSetAttribute(
+                           reinterpret_cast<const void*>(&k_rollout_generated<I, R, PL2>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize,
+                           static_cast<int>(lds)) == hipSuccess;
+          if (launched) {
+            k_rollout_generated<I, R, PL2><<<grid, kBlock, lds, st>>>(
+                *cfg, S, n_cand, n_steps, index_base, part, part_v, part_b);
+            launched = hipPeekAtLastError() == hipSuccess;
+          }
         },
         length_pow2(cfg->L));
-    k_finalize_gen<I, R><<<1, kFinBlock, 0, st>>>(part, static_cast<int>(grid), &S->h.K, part_v,
-                                                  part_b, n_steps, index_base, &S->h.incumbent,
-                                                  out, *cfg, hook);
+    // (a rollout that did not launch left no block records: no selection, the
+    // episode stays as it is)
+    if (launched)
+      k_finalize_gen<I, R><<<1, kFinBlock, 0, st>>>(part, static_cast<int>(grid), &S->h.K, part_v,
+                                                    part_b, n_steps, index_base, &S->h.incumbent,
+                                                    out, *cfg, hook);
   });
+  if (!launched) {
+    (void)hipGetLastError();
+    return MPC_ERR_HIP;
+  }
   return last_hip_status();
 }
 

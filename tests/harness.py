@@ -66,7 +66,33 @@ def replica_lib():
     L.replica_fulltree.argtypes = [ctypes.POINTER(MpcFulltreeProblem), _P, ctypes.c_int32, _P,
                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P,
                                    ctypes.POINTER(ctypes.c_int32), _P, ctypes.c_int64, _P]
+    L.replica_episode_layout.argtypes = [_P, ctypes.c_int32]
+    L.replica_episode_layout.restype = None
+    L.replica_consts.argtypes = [ctypes.POINTER(MpcProblem), _P]
+    L.replica_consts.restype = None
+    L.replica_cost.argtypes = [_P, ctypes.c_double, ctypes.c_double]
+    L.replica_cost.restype = ctypes.c_double
     return L
+
+
+def episode_layout(n):
+    """replica_episode_layout's first n values and the count it reports after them."""
+    out = np.full(n + 1, -1, dtype=np.int64)
+    replica_lib().replica_episode_layout(out.ctypes.data_as(_P), n + 1)
+    return [int(q) for q in out[:n]], int(out[n])
+
+
+def replica_consts(problem, nbytes):
+    """consts_from_problem(problem) as the library's host build forms it: raw bytes."""
+    buf = ctypes.create_string_buffer(nbytes)
+    replica_lib().replica_consts(ctypes.byref(problem), buf)
+    return buf.raw
+
+
+def replica_cost(consts_bytes, x, y):
+    """cost(x, y, K) of the library's host build, K = replica_consts' bytes."""
+    return float(replica_lib().replica_cost(ctypes.c_char_p(bytes(consts_bytes)), float(x),
+                                            float(y)))
 
 
 def device_rcp(q):

@@ -197,3 +197,72 @@ extern "C" int replica_fulltree(const mpc_fulltree_problem_t* p, const double* V
   return fulltree_impl<MPC_INTEG_QK21>(p, V, nv, B, nb, rot, device_consts != 0, costs, no_rot,
                                        leaves, n_leaves, traj);
 }
+
+// ---------------------------------------------------------------------------
+// The device-resident episode's state (mpc_episode.h) for tests/episode_state.py
+// and tests/episode_model.py: the layout of its structs as this compiler lays
+// them out, and the two host-buildable functions the episode's bookkeeping
+// takes its constants and its restart incumbent from.  Only the struct
+// definitions of mpc_episode.h are used: no device function is called.
+#include <stddef.h>
+
+// (mpc_episode.h also defines one kernel, k_episode_reset.  A host-only build
+// has no device image for a kernel's launch stub to register, so here it is
+// parsed as an ordinary device function, which the host build does not emit.
+// The macro is the HIP headers' own, already defined by the includes above,
+// and is put back right after this one include.)
+#include <hip/hip_runtime.h>
+#pragma push_macro("__global__")
+#undef __global__
+#define __global__ __device__
+#include "../diplomjourney_amd/csrc/mpc_episode.h"
+#pragma pop_macro("__global__")
+
+// out[0..n): sizeof of EpisodeHead, StaleTraj, EarlyPub, EpisodeState, Consts;
+// offsetof of every field of Consts, EpisodeHead, StaleTraj, EarlyPub,
+// EpisodeState, each in declaration order; kEpMaxGrid, kPubWords,
+// kStoredWords; last, the number of values before it (layout_names() of
+// tests/episode_state.py states the same order).
+extern "C" void replica_episode_layout(int64_t* out, int32_t n) {
+  using namespace mpc;
+#define OFF(S, f) static_cast<int64_t>(offsetof(S, f))
+  const int64_t v[] = {
+      sizeof(EpisodeHead), sizeof(StaleTraj), sizeof(EarlyPub), sizeof(EpisodeState),
+      sizeof(Consts),
+      OFF(Consts, x), OFF(Consts, y), OFF(Consts, phi), OFF(Consts, x_t), OFF(Consts, y_t),
+      OFF(Consts, x_0), OFF(Consts, y_0), OFF(Consts, A), OFF(Consts, B), OFF(Consts, C1),
+      OFF(Consts, C2), OFF(Consts, inv_den), OFF(Consts, L), OFF(Consts, inv_L), OFF(Consts, h),
+      OFF(Consts, hlgth), OFF(Consts, s0), OFF(Consts, c0), OFF(Consts, L_pow2),
+      OFF(Consts, pad_),
+      OFF(EpisodeHead, K), OFF(EpisodeHead, incumbent), OFF(EpisodeHead, x), OFF(EpisodeHead, y),
+      OFF(EpisodeHead, phi), OFF(EpisodeHead, v), OFF(EpisodeHead, beta), OFF(EpisodeHead, x_t),
+      OFF(EpisodeHead, y_t), OFF(EpisodeHead, x_0), OFF(EpisodeHead, y_0), OFF(EpisodeHead, t),
+      OFF(EpisodeHead, seed), OFF(EpisodeHead, step), OFF(EpisodeHead, p), OFF(EpisodeHead, m),
+      OFF(EpisodeHead, steps_for_slowing), OFF(EpisodeHead, episodes), OFF(EpisodeHead, nv),
+      OFF(EpisodeHead, nb), OFF(EpisodeHead, recursive), OFF(EpisodeHead, has_traj),
+      OFF(StaleTraj, ot), OFF(StaleTraj, v), OFF(StaleTraj, beta),
+      OFF(EarlyPub, step), OFF(EarlyPub, k), OFF(EarlyPub, alt), OFF(EarlyPub, t),
+      OFF(EarlyPub, h), OFF(EarlyPub, hl), OFF(EarlyPub, x), OFF(EarlyPub, y), OFF(EarlyPub, ph),
+      OFF(EpisodeState, h), OFF(EpisodeState, st), OFF(EpisodeState, early),
+      OFF(EpisodeState, grid_v), OFF(EpisodeState, grid_b), OFF(EpisodeState, done),
+      OFF(EpisodeState, chain_error), OFF(EpisodeState, p2p_seq), OFF(EpisodeState, chain_pub),
+      OFF(EpisodeState, gathered_tag),
+      kEpMaxGrid, kPubWords, kStoredWords};
+#undef OFF
+  const int32_t count = static_cast<int32_t>(sizeof(v) / sizeof(v[0]));
+  for (int32_t i = 0; i < n && i < count; ++i) out[i] = v[i];
+  if (n > count) out[count] = count;
+}
+
+// consts_from_problem (mpc_device.h), raw bytes: sizeof(Consts) at consts_out.
+extern "C" void replica_consts(const mpc_problem_t* p, void* consts_out) {
+  const mpc::Consts K = mpc::consts_from_problem(*p);
+  memcpy(consts_out, &K, sizeof(K));
+}
+
+// cost (mpc_device.h) of (x, y) under the constants replica_consts wrote.
+extern "C" double replica_cost(const void* consts, double x, double y) {
+  mpc::Consts K;
+  memcpy(&K, consts, sizeof(K));
+  return mpc::cost(x, y, K);
+}
