@@ -17,6 +17,7 @@
 #include "mpc_episode.h"
 #include "mpc_exchange.h"
 #include "mpc_finalize.h"
+#include "mpc_kernels.h"
 #include "mpc_lanes.h"
 #include "mpc_winner.h"
 
@@ -131,12 +132,20 @@ constexpr int chain_waves() {
 // form, whose records block 0 of the SAME launch collects).  WAIT_TICKS bounds
 // the wait for block 0's constants (kChainWaitTicks on one GPU,
 // kXchgWaitTicks when block 0 itself waits for peers or a collective).
-template <int INTEG, int ROT, bool PL2, bool TAGGED, uint64_t WAIT_TICKS, bool TILED>
+// Obs (mpc_episode_obs.h FrameObs; NoObs: none): keep-out circles.  The loop
+// tests them in the frame of the sums, so the table needs the step's final
+// pose before the loop: an obstacle block that does not find the constants
+// final in pre0 waits for them there (the same bounded wait, the same
+// chain_error) and speculates nothing; obs.form() then makes the table.
+// n_blocked: as in rollout_argmin_body.
+template <int INTEG, int ROT, bool PL2, bool TAGGED, uint64_t WAIT_TICKS, bool TILED,
+          class Obs = NoObs>
 __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32_t epoch,
                                             const double* __restrict__ v,
                                             const double* __restrict__ b, int64_t n_cand,
                                             int n_steps, Rec* __restrict__ part, int has_prev,
-                                            const mpc_episode_config_t& ecfg) {
+                                            const mpc_episode_config_t& ecfg, Obs obs = Obs{},
+                                            unsigned long long* __restrict__ n_blocked = nullptr) {
   constexpr int CPL = 2;
   __shared__ __attribute__((aligned(16))) uint32_t s_w[kPubWords];
   __shared__ uint32_t s_tag[kPubWords];
@@ -166,6 +175,7 @@ __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32
     }
     __syncthreads();
     Kl = consts_from_words(s_w);
+    if constexpr (Obs::kOn) return;   // (first(), below: waits instead of speculating)
     if (s_final) return;
     // speculate h from the published t: the previous step's (+ dt) or, if
     // block 0 already published it, this step's; torn -> NaN (recompute)
@@ -240,6 +250,17 @@ __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32
       __syncthreads();
     }
   };
+  // What the lane calls once its first control loads are in flight.
+  auto first = [&]() {
+    pre0();
+    if constexpr (Obs::kOn) {
+      if (!s_final) {   // (uniform over the block)
+        wait();
+        Kl = consts_from_words(s_w);
+      }
+      obs.form(Kl, PL2);
+    }
+  };
   // 32-bit candidate indices (the aligned path's rows are < 2^28 candidates,
   // wide_ok): the clamp below is one v_min with a scalar operand, no 64-bit
   // select holding its own registers across the loop
@@ -247,24 +268,34 @@ __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32
   const int32_t n_tiles = (n32 + kBlock * CPL - 1) / (kBlock * CPL);
   uint64_t best_k = ~0ull;
   int64_t best_i = INT64_MAX;
+  [[maybe_unused]] uint32_t wave_blocked = 0;   // (wave-uniform)
   for (int32_t tile = blockIdx.x - 1; tile < n_tiles; tile += gridDim.x - 1) {
     const int32_t c0 = tile * (kBlock * CPL) + static_cast<int32_t>(threadIdx.x) * CPL;
     // lanes past the end of a partial tile roll the last pair again (result
     // ignored), so every lane reaches the barriers of pre0 / wait on the same path
     const int32_t cl = min(c0, n32 - CPL);
     double cst[CPL];
+    [[maybe_unused]] bool blocked[CPL];
     // leading trig coefficients not pinned: the fifth wave per SIMD needs the
     // registers more (as the rect+cum stream kernel)
     // TILED: the tile's rows are one contiguous run (tile base + s * 1024
     // doubles), the lane's column its offset within the tile
     const int64_t tb0 = TILED ? static_cast<int64_t>(tile) * (2 * MPC_TILE) * n_steps : 0;
-    rollout_lane_glds_k<INTEG, ROT, PL2, decltype(wait), decltype(pre0), decltype(mid),
-                        false>(K, Kl, v + tb0, b + tb0, TILED ? 2 * MPC_TILE : n_cand,
-                               TILED ? cl - tile * MPC_TILE : cl, n_steps, cst, wait, pre0, mid);
+    rollout_lane_glds_k<INTEG, ROT, PL2, decltype(wait), decltype(first), decltype(mid), false,
+                        Obs>(K, Kl, v + tb0, b + tb0, TILED ? 2 * MPC_TILE : n_cand,
+                             TILED ? cl - tile * MPC_TILE : cl, n_steps, cst, wait, first, mid, obs,
+                             blocked);
+    if constexpr (Obs::kOn) {   // (every lane: the clamped lanes' repeats are not counted)
+#pragma unroll
+      for (int j = 0; j < CPL; ++j)
+        wave_blocked +=
+            __builtin_popcountll(__builtin_amdgcn_ballot_w64(blocked[j] && c0 < n32));
+    }
     if (c0 < n32) {
 #pragma unroll
       for (int j = 0; j < CPL; ++j) {
-        const uint64_t kk = cost_key_nonneg(cst[j]);
+        uint64_t kk = cost_key_nonneg(cst[j]);
+        if constexpr (Obs::kOn) kk = blocked[j] ? ~0ull : kk;
         if (kk < best_k) {
           best_k = kk;
           best_i = c0 + j;
@@ -272,12 +303,23 @@ __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32
       }
     }
   }
+  if constexpr (Obs::kOn) {
+    if ((threadIdx.x & 63) == 0) blocked_slots()[threadIdx.x >> 6] = wave_blocked;
+  }   // (block_argmin's barrier orders these stores before thread 0's reads)
   block_argmin<true>(best_k, best_i);   // (indices < n_cand < 2^31)
   if (threadIdx.x == 0) {
     if constexpr (TAGGED)
       store_tagged_rec(&part[blockIdx.x - 1], best_k, best_i, epoch);
     else
       part[blockIdx.x - 1] = Rec{best_k, best_i};
+  }
+  if constexpr (Obs::kOn) {
+    if (threadIdx.x == 0 && n_blocked) {
+      uint32_t total = 0;
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) total += blocked_slots()[w];
+      if (total) atomicAdd(n_blocked, static_cast<unsigned long long>(total));
+    }
   }
 }
 

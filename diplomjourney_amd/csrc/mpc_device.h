@@ -6,6 +6,7 @@
 //   quad_const, heading_incr, position_step, step_core, step_start, cum_pose,
 //   step_safe, crit_sqrt, cost      one step and the criterion
 //   Circle .. ObsTable, NoObs, CircleObs   keep-out circles: tables and lane hooks
+//   frame_circle                    a circle in the frame of the rect+cum sums
 //   rollout_candidate_l, rollout_candidate  one candidate as the kernels evaluate it
 //
 // Every function here states one piece of ShittyWizard/DiplomJourney's
@@ -353,6 +354,19 @@ struct CircleObs {
     blocked = bl[0];
   }
 };
+
+// One world-table circle (centre, r^2) in the frame of the kRotCum sums of the
+// step that starts at K's pose: the `loop` entry host_obstacles forms on the
+// host, for the entries whose pose exists only on the device (the episode
+// steps, mpc_episode_obs.h).  A = c0 dx + s0 dy, B = c0 dy - s0 dx with (dx, dy)
+// the centre minus the start position — the inverse of cum_pose — and, for the
+// 1/L-scaled sums of PL2, centre times 1/L and r^2 times 1/L^2 (L a power of
+// two: (r / L)^2 exactly).  An unused entry (r2 = -1) stays one.
+MPC_HD __forceinline__ Circle frame_circle(const Consts& K, const Circle& w, bool scaled) {
+  const double sc = scaled ? K.inv_L : 1.0;
+  const double dx = w.cx - K.x, dy = w.cy - K.y;
+  return Circle{(K.c0 * dx + K.s0 * dy) * sc, (K.c0 * dy - K.s0 * dx) * sc, w.r2 * (sc * sc), 0.0};
+}
 
 // One candidate, exactly as the kernels evaluate it (the host replica in
 // tests/replica_harness.cpp calls this): the core recurrence, and if that

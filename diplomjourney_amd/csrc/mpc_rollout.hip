@@ -2,7 +2,8 @@
 // the MPC candidate expansion (ShittyWizard/DiplomJourney
 // math_model_tree.py:278-362).  Kernels: mpc_kernels.h (rollout + arg-min,
 // selection), mpc_finalize.h, mpc_sampler.h, and the device-resident episode's
-// (mpc_episode.h, mpc_generated.h, mpc_exchange.h, mpc_chain.h, mpc_run.h);
+// (mpc_episode.h, mpc_generated.h, mpc_exchange.h, mpc_chain.h, mpc_run.h,
+// mpc_episode_obs.h: the steps with keep-out circles);
 // the host's problem constants: mpc_host_consts.h.
 //
 // HBM traffic of k_rollout_argmin: 16 B per candidate-step read once
@@ -24,6 +25,7 @@
 #include "mpc_comm.h"
 #include "mpc_device.h"
 #include "mpc_episode.h"
+#include "mpc_episode_obs.h"
 #include "mpc_episodes.h"
 #include "mpc_exchange.h"
 #include "mpc_finalize.h"
@@ -300,6 +302,51 @@ void launch_rollout_obs(hipStream_t st, int32_t integrator, const Consts& K, con
   });
 }
 
+// The episode entries' table: the circles in world coordinates alone (the
+// rect+cum frame table is formed on the device, mpc_episode_obs.h).
+Obstacles world_obstacles(const mpc_obstacle_t* obs, int n) {
+  Obstacles W;
+  for (int i = 0; i < MPC_MAX_OBSTACLES; ++i) W.c[i] = Circle{0.0, 0.0, -1.0, 0.0};
+  for (int i = 0; i < n; ++i) W.c[i] = Circle{obs[i].x, obs[i].y, obs[i].r * obs[i].r, 0.0};
+  return W;
+}
+
+// n_obs -> f(IC<NOBS>) over the instantiations: 4 or all, and with ONE also 1.
+template <bool ONE, class F>
+void dispatch_nobs(int n_obs, F&& f) {
+  if constexpr (ONE) {
+    if (n_obs <= 1) return f(IC<1>{});
+  }
+  if (n_obs <= 4)
+    f(IC<4>{});
+  else
+    f(IC<MPC_MAX_OBSTACLES>{});
+}
+
+// launch_rollout<true> with circles: the same grid and path choice.
+void launch_episode_obs(hipStream_t st, int32_t integrator, const Obstacles& W, int n_obs,
+                        const Consts* Kdev, const double* v, const double* b, int64_t n_cand,
+                        int n_steps, Rec* part, unsigned long long* n_blocked) {
+  const bool wide = wide_ok(v, b, n_cand);
+  dispatch_mode(integrator, [&](auto I, auto R) {
+    if (wide)
+      dispatch_nobs<true>(n_obs, [&](auto NOBS) {
+        k_episode_stream_obs<I, R, NOBS><<<rollout_grid<kCplWide>(n_cand), kBlock, 0, st>>>(
+            W, Kdev, v, b, n_cand, n_steps, part, n_blocked);
+      });
+    else
+      k_episode_argmin_obs<I, R, MPC_MAX_OBSTACLES><<<rollout_grid<1>(n_cand), kBlock, 0, st>>>(
+          W, Kdev, v, b, n_cand, n_steps, part, n_blocked);
+  });
+}
+
+// n_blocked_out of the episode obstacle entries: zeroed on the stream.
+int zero_blocked(int64_t* n_blocked_out, hipStream_t st) {
+  if (n_blocked_out && hipMemsetAsync(n_blocked_out, 0, sizeof(*n_blocked_out), st) != hipSuccess)
+    return MPC_ERR_HIP;
+  return MPC_OK;
+}
+
 template <bool KDEV>
 void launch_finalize(hipStream_t st, int32_t integrator, const Rec* part, int n_part,
                      const Consts& K, const Consts* Kdev, const double* v, const double* b,
@@ -359,6 +406,31 @@ bool chained_args_ok(const mpc_episode_config_t* cfg, const void* state, const v
 // The chained kernels' one mode: rect + cumulative heading.
 bool chained_mode_ok(int32_t integrator, bool allow_tiled) {
   return mode_ok(integrator, true, allow_tiled) == MPC_OK && is_cum(integrator);
+}
+
+// mpc_episode_chain_step (and its obstacle form): every check, in that order;
+// *has_prev: a previous step is to be completed.
+int check_chain_step(const mpc_episode_config_t* cfg, const void* state, int32_t mode,
+                     uint32_t epoch, const double* v_sc, const double* beta_sc, int64_t n_cand,
+                     int32_t n_steps, int64_t index_base, int32_t integrator, const void* ws,
+                     const void* ws_prev, size_t ws_bytes, const double* v_prev,
+                     const double* beta_prev, const mpc_result_t* out_prev, int32_t log_capacity,
+                     int* has_prev) {
+  if (!chained_args_ok(cfg, state, v_sc, beta_sc, n_cand, n_steps, index_base, log_capacity,
+                       epoch) ||
+      mode != MPC_CHAIN_FINALIZE)
+    return MPC_ERR_ARG;
+  if (!chained_mode_ok(integrator, true) || !chain_ctl_ok(v_sc, beta_sc, n_cand, integrator))
+    return MPC_ERR_UNSUPPORTED;
+  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
+  *has_prev = 0;
+  if (v_prev) {
+    if (!beta_prev || !out_prev || !ws_prev || !chain_ctl_ok(v_prev, beta_prev, n_cand, integrator))
+      return MPC_ERR_ARG;
+    *has_prev = 1;
+  }
+  if (!wall_clock_ok()) return MPC_ERR_UNSUPPORTED;
+  return MPC_OK;
 }
 
 // mpc_episode_finalize / mpc_episode_rollout: the same checks in the same
@@ -770,6 +842,42 @@ int mpc_episode_step(void* state, const double* v_sc, const double* beta_sc, int
                               ws_bytes, out, advance, log, log_capacity, stream);
 }
 
+int mpc_episode_partials_obstacles(void* state, const mpc_obstacle_t* obstacles,
+                                   int32_t n_obstacles, const double* v_sc,
+                                   const double* beta_sc, int64_t n_cand, int32_t n_steps,
+                                   int32_t integrator, void* ws, size_t ws_bytes,
+                                   int64_t* n_blocked_out, mpc_stream_t stream) {
+  if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
+  if (check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK) return MPC_ERR_ARG;
+  if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
+  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (zero_blocked(n_blocked_out, st) != MPC_OK) return MPC_ERR_HIP;
+  if (n_obstacles == 0)   // the kernels without obstacles: nothing can be blocked
+    return mpc_episode_partials(state, v_sc, beta_sc, n_cand, n_steps, integrator, ws, ws_bytes,
+                                stream);
+  EpisodeState* S = static_cast<EpisodeState*>(state);
+  launch_episode_obs(st, integrator, world_obstacles(obstacles, n_obstacles), n_obstacles,
+                     &S->h.K, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws),
+                     reinterpret_cast<unsigned long long*>(n_blocked_out));
+  return last_hip_status();
+}
+
+int mpc_episode_step_obstacles(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                               const double* v_sc, const double* beta_sc, int64_t n_cand,
+                               int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
+                               size_t ws_bytes, mpc_result_t* out,
+                               const mpc_episode_config_t* advance, mpc_episode_log_t* log,
+                               int32_t log_capacity, int64_t* n_blocked_out,
+                               mpc_stream_t stream) {
+  const int a = mpc_episode_partials_obstacles(state, obstacles, n_obstacles, v_sc, beta_sc, n_cand,
+                                               n_steps, integrator, ws, ws_bytes, n_blocked_out,
+                                               stream);
+  if (a != MPC_OK) return a;
+  return mpc_episode_finalize(state, v_sc, beta_sc, n_cand, n_steps, index_base, integrator, ws,
+                              ws_bytes, out, advance, log, log_capacity, stream);
+}
+
 int mpc_episode_rollout(void* state, const double* v_sc, const double* beta_sc, int64_t n_cand,
                         int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
                         size_t ws_bytes, mpc_result_t* out, const mpc_episode_config_t* advance,
@@ -805,20 +913,11 @@ int mpc_episode_chain_step(const mpc_episode_config_t* cfg, void* state, int32_t
                            mpc_episode_log_t* log, int32_t log_capacity, mpc_stream_t stream) {
   (void)gathered;
   (void)n_gathered;
-  if (!chained_args_ok(cfg, state, v_sc, beta_sc, n_cand, n_steps, index_base, log_capacity,
-                       epoch) ||
-      mode != MPC_CHAIN_FINALIZE)
-    return MPC_ERR_ARG;
-  if (!chained_mode_ok(integrator, true) || !chain_ctl_ok(v_sc, beta_sc, n_cand, integrator))
-    return MPC_ERR_UNSUPPORTED;
-  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
   int has_prev = 0;
-  if (v_prev) {
-    if (!beta_prev || !out_prev || !ws_prev || !chain_ctl_ok(v_prev, beta_prev, n_cand, integrator))
-      return MPC_ERR_ARG;
-    has_prev = 1;
-  }
-  if (!wall_clock_ok()) return MPC_ERR_UNSUPPORTED;
+  const int a = check_chain_step(cfg, state, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
+                                 index_base, integrator, ws, ws_prev, ws_bytes, v_prev, beta_prev,
+                                 out_prev, log_capacity, &has_prev);
+  if (a != MPC_OK) return a;
   EpisodeState* S = static_cast<EpisodeState*>(state);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // block 0 + one block per tile; the previous step's records are as many
@@ -832,6 +931,42 @@ int mpc_episode_chain_step(const mpc_episode_config_t* cfg, void* state, int32_t
                 S, epoch, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws), has_prev,
                 static_cast<const Rec*>(ws_prev), n_part_prev, v_prev, beta_prev, index_base,
                 out_prev, nullptr, 0, *cfg, log, log_capacity, 0u);
+      },
+      length_pow2(cfg->L), is_tiled(integrator));
+  return last_hip_status();
+}
+
+int mpc_episode_chain_step_obstacles(
+    const mpc_episode_config_t* cfg, void* state, const mpc_obstacle_t* obstacles,
+    int32_t n_obstacles, int32_t mode, uint32_t epoch, const double* v_sc, const double* beta_sc,
+    int64_t n_cand, int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
+    const void* ws_prev, size_t ws_bytes, const double* v_prev, const double* beta_prev,
+    mpc_result_t* out_prev, const mpc_result_t* gathered, int32_t n_gathered,
+    mpc_episode_log_t* log, int32_t log_capacity, int64_t* n_blocked_out, mpc_stream_t stream) {
+  if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
+  int has_prev = 0;
+  const int a = check_chain_step(cfg, state, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
+                                 index_base, integrator, ws, ws_prev, ws_bytes, v_prev, beta_prev,
+                                 out_prev, log_capacity, &has_prev);
+  if (a != MPC_OK) return a;
+  EpisodeState* S = static_cast<EpisodeState*>(state);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (zero_blocked(n_blocked_out, st) != MPC_OK) return MPC_ERR_HIP;
+  if (n_obstacles == 0)   // the base entry: the same kernels, nothing can be blocked
+    return mpc_episode_chain_step(cfg, state, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
+                                  index_base, integrator, ws, ws_prev, ws_bytes, v_prev, beta_prev,
+                                  out_prev, gathered, n_gathered, log, log_capacity, stream);
+  const Obstacles W = world_obstacles(obstacles, n_obstacles);
+  const int64_t tiles = rollout_grid<kCplWide>(n_cand);
+  dispatch_bools(
+      [&](auto PL2, auto TILED) {
+        dispatch_nobs<false>(n_obstacles, [&](auto NOBS) {
+          k_episode_chain_obs<PL2, TILED, NOBS><<<tiles + 1, kBlock, 0, st>>>(
+              W, S, epoch, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws), has_prev,
+              static_cast<const Rec*>(ws_prev), static_cast<int>(tiles), v_prev, beta_prev,
+              index_base, out_prev, *cfg, log, log_capacity,
+              reinterpret_cast<unsigned long long*>(n_blocked_out));
+        });
       },
       length_pow2(cfg->L), is_tiled(integrator));
   return last_hip_status();

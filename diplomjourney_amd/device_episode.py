@@ -8,7 +8,7 @@ import torch
 
 from . import native
 from .abi import (CANDIDATE_BYTES, INTEGRATORS, IPC_HANDLE_BYTES, LOG_BYTES, MPC_LAYOUT_TILED,
-                  MPC_TILE, RESULT_BYTES, MpcEpisodeLog)
+                  MPC_MAX_OBSTACLES, MPC_TILE, RESULT_BYTES, MpcEpisodeLog, make_obstacles)
 from .distributed import gather_bytes, gather_into, gather_results, reduce_int, shard_range
 from .episode_config import ChainError, reference_episode_config
 from .streams import _check_overlap_stream
@@ -37,16 +37,21 @@ class _ChainForm:
 
 
 class _OneGpuChain(_ChainForm):
-    """mpc_episode_chain_step / mpc_episode_finalize."""
+    """mpc_episode_chain_step (with circles: _chain_step_obstacles) /
+    mpc_episode_finalize."""
     pends_controls = True
 
     def launch(self, ep, ctl, pend, events):
         vp, bp, integ = ep._ptrs(ctl)
         ws, ws_prev = ep._ws
-        ep._C.mpc_episode_chain_step(
-            *ep._head, 1, ep._next_epoch(), vp, bp, *ep._shard, integ, ws.data_ptr(),
-            ws_prev.data_ptr(), ws.numel(), *ep._prev_ptrs(pend), ep.local.data_ptr(), None, 0,
-            *ep._tail())
+        args = (1, ep._next_epoch(), vp, bp, *ep._shard, integ, ws.data_ptr(),
+                ws_prev.data_ptr(), ws.numel(), *ep._prev_ptrs(pend), ep.local.data_ptr(), None, 0)
+        if ep._n_obs or ep._obstacle_entries:
+            log, cap, st = ep._tail()
+            ep._C.mpc_episode_chain_step_obstacles(*ep._head, *ep._circles(), *args, log, cap,
+                                                   ep._blocked_ptr(), st)
+        else:
+            ep._C.mpc_episode_chain_step(*ep._head, *args, *ep._tail())
         _stop(events)
         return ctl
 
@@ -225,13 +230,30 @@ class DeviceEpisode:
     sequence with `flush()` inside the capture.  A replay repeats the captured
     launches' epochs; the flush's update clears the published constants' tags,
     without it the next replay's launch with the last epoch could accept the
-    previous replay's constants (include/mpc_rollout.h)."""
+    previous replay's constants (include/mpc_rollout.h).
+
+    obstacles / set_obstacles(): keep-out circles (x, y, r) in world
+    coordinates, at most 16, with the semantics of the one-shot entries
+    (mpc_rollout_partials_obstacles): a candidate that ends a step strictly
+    inside one never wins; if all do, the step has no winner (MPC_EP_STALE).
+    `n_blocked` (device int64) holds the blocked candidates of the last
+    rollout.  Supported with circles: the two-launch step (split=True; sampler
+    or caller controls, also expand() + advance() across ranks) and the
+    one-GPU chained step (chain=True, SoA or tiled).  A chained tile block
+    needs the step's pose before its rollout, so it waits for block 0 first:
+    with circles the chained step gives up the overlap it exists for.  At
+    config C it is still the faster form with 4 circles (40.3 against 43.4 us
+    per step), level with 16 (65.6 / 65.7 us) and SLOWER than the two-launch
+    step with one (40.4 against 39.7 us); counting n_blocked adds ~5 us to
+    either.  Not supported, ValueError: generate,
+    split=False, the chained exchange / P2P / overlapped steps, run().  With no
+    circles every call is the one made without the feature."""
 
     def __init__(self, engine, n_cand_total, n_steps, rank=0, world=1, seed=20261015,
                  integrator="rect", group=None, start=(0.0, 0.0, 0.0, 0.0, 0.0), target=(2, 3),
                  log_capacity=4096, split=True, exchange=None, chain=False, L=None,
                  generate=False, max_steps=0, incumbent0=0.0, enumerate=False, overlap=False,
-                 p2p=False, mailbox_uncached=True):
+                 p2p=False, mailbox_uncached=True, obstacles=()):
         self.eng = engine
         self.lib = native.lib()           # entries that return their status (callers, tests)
         self._C = native.calls()          # entries that raise
@@ -275,6 +297,9 @@ class DeviceEpisode:
         # last one.  The workspaces alternate.
         self.chain = bool(chain)
         self._ws = [self.ws, torch.zeros_like(self.ws)] if self.chain else [self.ws]
+        self.generate = bool(generate)
+        if len(obstacles) and not self._takes_obstacles():
+            raise ValueError(self._OBSTACLE_FORMS)
         # exchange + chain: this rank's best candidate of the step (the
         # all_gather payload of mpc_episode_exchange_step)
         self.cand = torch.zeros(CANDIDATE_BYTES, dtype=torch.uint8, device=dev)
@@ -301,7 +326,6 @@ class DeviceEpisode:
         # generate: steps without caller controls draw their candidates inside
         # the rollout (mpc_episode_generate_step) instead of sampling them into
         # v_sc / b_sc first — the same candidates, never written to HBM
-        self.generate = bool(generate)
         if self.generate and self.exchange:
             raise ValueError("generated controls: one GPU (no exchange step)")
         self._gen_ws = None               # workspace of the generated step
@@ -310,7 +334,39 @@ class DeviceEpisode:
         self._epoch = 0
         self._checked = {}
         self.steps_enqueued = 0
+        self.n_blocked = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._obs, self._n_obs = None, 0
+        # (tools/episode_obstacle_cost.py: take the obstacle entries with no
+        # circles too, to time their dispatch of the plain kernels)
+        self._obstacle_entries = False
+        self._count_blocked = True      # (the same tool: n_blocked's memset costs ~5 us a step)
+        self.set_obstacles(obstacles)
         self.reset(_fresh_mailbox=True)
+
+    _OBSTACLE_FORMS = ("keep-out circles: the two-launch step (split=True, generate=False) and "
+                       "the one-GPU chained step (chain=True, exchange=False) only")
+
+    def set_obstacles(self, circles):
+        """The keep-out circles of the steps enqueued from now on (a pending
+        chained step is completed first; its rollout already ran under the
+        previous circles)."""
+        obs, n = make_obstacles(circles)
+        if n > MPC_MAX_OBSTACLES:
+            raise ValueError(f"at most {MPC_MAX_OBSTACLES} obstacles")
+        if n and not self._takes_obstacles():
+            raise ValueError(self._OBSTACLE_FORMS)
+        if self._pending is not None:
+            self.flush()
+        self._obs, self._n_obs = obs, n
+
+    def _takes_obstacles(self):
+        return self.split and not self.generate and not (self.chain and self.exchange)
+
+    def _blocked_ptr(self):
+        return self.n_blocked.data_ptr() if self._count_blocked else None
+
+    def _circles(self):
+        return self._obs, self._n_obs
 
     def _p2p_setup(self, dev, uncached):
         """The mailbox's three stages (_Mailbox), the ranks' verdict reduced
@@ -466,6 +522,8 @@ class DeviceEpisode:
         first."""
         if self.exchange:
             raise ValueError("the persistent run: one GPU (no exchange step)")
+        if self._n_obs:
+            raise ValueError("run(): " + self._OBSTACLE_FORMS)
         if self.integrator != "rect+cum" or self.n_local % 2:
             raise ValueError("the persistent run streams rect+cum candidates, n_local even")
         batches = list(batches)
@@ -559,7 +617,12 @@ class DeviceEpisode:
                 self.log.data_ptr() if one_gpu else None, self.log_capacity if one_gpu else 0, st)
         if events:
             events[0].record()
-        if self.split and not events:
+        if (self._n_obs or self._obstacle_entries) and not events:
+            # (split, checked by set_obstacles) the same two launches, the
+            # rollout with circles
+            C.mpc_episode_step_obstacles(args[0], *self._circles(), *args[1:-1],
+                                         self._blocked_ptr(), st)
+        elif self.split and not events:
             # streaming kernel, then the selection kernel: two launches in one
             # host call (the faster form on MI355X: 44.8 vs 47.5 us per
             # config-C step than the one-launch form below)
@@ -581,10 +644,16 @@ class DeviceEpisode:
         if _is_tiled(self.cur):
             raise ValueError("the streaming kernel alone reads SoA controls")
         v, b = self.cur
+        st = st if st is not None else native.current_stream()
+        if self._n_obs or self._obstacle_entries:
+            self._C.mpc_episode_partials_obstacles(
+                self.state.data_ptr(), *self._circles(), v.data_ptr(), b.data_ptr(), self.n_local,
+                self.n_steps, self._integ, self.ws.data_ptr(), self.ws.numel(),
+                self._blocked_ptr(), st)
+            return
         self._C.mpc_episode_partials(
             self.state.data_ptr(), v.data_ptr(), b.data_ptr(), self.n_local,
-            self.n_steps, self._integ, self.ws.data_ptr(), self.ws.numel(),
-            st if st is not None else native.current_stream())
+            self.n_steps, self._integ, self.ws.data_ptr(), self.ws.numel(), st)
 
     def advance(self):
         """Multi-GPU: all_gather of the per-rank winners (RCCL) + selection +

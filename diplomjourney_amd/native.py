@@ -77,6 +77,14 @@ PROTOTYPES = {
     "mpc_episode_step": (c_int, _FINALIZE),
     "mpc_episode_chain_step": (c_int, [_CFG, _P, _I32, c_uint32, _P, _P, _I64, _I32, _I64, _I32,
                                        _P, _P, c_size_t, _P, _P, _P, _P, _I32, _P, _I32, _P]),
+    # ... with keep-out circles: the base entry's arguments, + (circles, count)
+    # after the state, + n_blocked_out before the stream
+    "mpc_episode_partials_obstacles": (c_int, [_P, _P, _I32, _P, _P, _I64, _I32, _I32, _P,
+                                               c_size_t, _P, _P]),
+    "mpc_episode_step_obstacles": (c_int, _FINALIZE[:1] + [_P, _I32] + _FINALIZE[1:-1] + [_P, _P]),
+    "mpc_episode_chain_step_obstacles": (c_int, [_CFG, _P, _P, _I32, _I32, c_uint32, _P, _P, _I64,
+                                                 _I32, _I64, _I32, _P, _P, c_size_t, _P, _P, _P,
+                                                 _P, _I32, _P, _I32, _P, _P]),
     "mpc_episode_run_workspace_bytes": (c_size_t, [_I64]),
     "mpc_episode_run": (c_int, [_CFG, _P, c_uint32, _PP, _PP, _I32, _I64, _I32, _I64, _I32, _P,
                                 c_size_t, _P, _P, _I32, _P]),

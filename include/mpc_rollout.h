@@ -181,7 +181,9 @@ int mpc_rollout_finalize(const mpc_problem_t* p, const double* v_sc, const doubl
  * mpc_rollout_finalize).  MPC_ERR_ARG, before any HIP call: n_obstacles
  * outside [0, MPC_MAX_OBSTACLES], obstacles NULL with n_obstacles > 0, a
  * non-finite centre, r not finite or r <= 0.  The device-resident episode
- * entries, the batched entry and the full tree take no obstacles.
+ * takes circles through mpc_episode_partials_obstacles, _step_obstacles and
+ * _chain_step_obstacles (below, where what still takes none is listed); the
+ * batched entry and the full tree take no obstacles.
  */
 #define MPC_MAX_OBSTACLES 16
 typedef struct mpc_obstacle {
@@ -398,6 +400,56 @@ int mpc_episode_chain_step(const mpc_episode_config_t* cfg, void* state, int32_t
                            const double* beta_prev, mpc_result_t* out_prev,
                            const mpc_result_t* gathered, int32_t n_gathered,
                            mpc_episode_log_t* log, int32_t log_capacity, mpc_stream_t stream);
+
+/* Keep-out circles in the device-resident steps: the semantics of
+ * mpc_rollout_partials_obstacles (world-frame circles {x, y, r}, at most
+ * MPC_MAX_OBSTACLES, step-end states strictly inside block a candidate, the
+ * step's start pose is not tested, a NaN state is inside nothing, a blocked
+ * candidate never wins).  If every candidate is blocked the step has no
+ * winner and the episode update takes its `found == 0` branch (MPC_EP_STALE:
+ * the stale trajectory, or the pose itself before any winner).
+ * Each entry takes its base entry's arguments, plus `obstacles, n_obstacles`
+ * after `state` (a host array, read during the call only: the circles travel
+ * as kernel arguments, so a captured graph keeps them), plus n_blocked_out
+ * (optional device int64, zeroed on `stream`, then the number of blocked
+ * candidates of this call's rollout) before `stream`.
+ *   mpc_episode_partials_obstacles    mpc_episode_partials with circles: all
+ *                                     five modes, aligned and scalar path
+ *   mpc_episode_step_obstacles        that + the unchanged mpc_episode_finalize
+ *   mpc_episode_chain_step_obstacles  mpc_episode_chain_step with circles: the
+ *       launch's tile blocks test THIS step's candidates, its first block
+ *       completes the previous step as ever; the chain is still ended by
+ *       mpc_episode_finalize.  rect+cum tests the circles in the frame of the
+ *       step's start pose, so a tile block waits for the published pose before
+ *       its rollout instead of after it (the same bounded wait and chain error).
+ * MPC_ERR_ARG before any HIP call for the circles (as
+ * mpc_rollout_partials_obstacles); with valid circles every other rejection
+ * is the base entry's.  n_obstacles == 0 calls the base entry: the same
+ * kernels, the same bytes.  EpisodeState and the block records are unchanged,
+ * so finalize, the update and the multi-GPU expand / advance step follow as
+ * they are.  Without obstacles: the fused step (mpc_episode_rollout), the
+ * generated step, the persistent run, the exchange and P2P chained steps,
+ * mpc_episodes_run, the batched entry and the full tree. */
+int mpc_episode_partials_obstacles(void* state, const mpc_obstacle_t* obstacles,
+                                   int32_t n_obstacles, const double* v_sc,
+                                   const double* beta_sc, int64_t n_cand, int32_t n_steps,
+                                   int32_t integrator, void* ws, size_t ws_bytes,
+                                   int64_t* n_blocked_out, mpc_stream_t stream);
+int mpc_episode_step_obstacles(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                               const double* v_sc, const double* beta_sc, int64_t n_cand,
+                               int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
+                               size_t ws_bytes, mpc_result_t* out,
+                               const mpc_episode_config_t* advance, mpc_episode_log_t* log,
+                               int32_t log_capacity, int64_t* n_blocked_out,
+                               mpc_stream_t stream);
+int mpc_episode_chain_step_obstacles(
+    const mpc_episode_config_t* cfg, void* state, const mpc_obstacle_t* obstacles,
+    int32_t n_obstacles, int32_t mode, uint32_t epoch, const double* v_sc, const double* beta_sc,
+    int64_t n_cand, int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
+    const void* ws_prev, size_t ws_bytes, const double* v_prev, const double* beta_prev,
+    mpc_result_t* out_prev, const mpc_result_t* gathered, int32_t n_gathered,
+    mpc_episode_log_t* log, int32_t log_capacity, int64_t* n_blocked_out, mpc_stream_t stream);
+
 /* Persistent run (one GPU, integrator MPC_INTEG_RECT | MPC_HEADING_CUMULATIVE,
  * SoA or MPC_LAYOUT_TILED controls under the chained step's rules): n_run
  * COMPLETE MPC steps of the episode — step j over the caller-resident controls
