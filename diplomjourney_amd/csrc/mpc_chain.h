@@ -3,8 +3,11 @@
 //
 //   kChainFin, kChainXchg, kChainP2P   what block 0 completes the previous step with
 //   consts_from_words, chain_read      the published constants, as a tile block reads them
-//   chain_waves, chain_tiles           the tile blocks
-//   k_episode_chain                    block 0 (mpc_finalize.h / mpc_exchange.h) + the tiles
+//   chain_waves, chain_tiles           the tile blocks (with an obstacle hook: the
+//                                      blocked-count epilogue of mpc_kernels.h)
+//   k_episode_chain                    block 0 (mpc_finalize.h / mpc_exchange.h) + the tiles;
+//                                      its kChainFin block 0 is repeated in
+//                                      k_episode_chain_obs (mpc_episode_obs.h)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -303,9 +306,7 @@ __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32
       }
     }
   }
-  if constexpr (Obs::kOn) {
-    if ((threadIdx.x & 63) == 0) blocked_slots()[threadIdx.x >> 6] = wave_blocked;
-  }   // (block_argmin's barrier orders these stores before thread 0's reads)
+  if constexpr (Obs::kOn) store_wave_blocked(wave_blocked);
   block_argmin<true>(best_k, best_i);   // (indices < n_cand < 2^31)
   if (threadIdx.x == 0) {
     if constexpr (TAGGED)
@@ -313,14 +314,7 @@ __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32
     else
       part[blockIdx.x - 1] = Rec{best_k, best_i};
   }
-  if constexpr (Obs::kOn) {
-    if (threadIdx.x == 0 && n_blocked) {
-      uint32_t total = 0;
-#pragma unroll
-      for (int w = 0; w < kWaves; ++w) total += blocked_slots()[w];
-      if (total) atomicAdd(n_blocked, static_cast<unsigned long long>(total));
-    }
-  }
+  if constexpr (Obs::kOn) add_block_blocked(n_blocked);
 }
 
 template <int INTEG, int ROT, int MODE, bool PL2, bool TILED = false>
@@ -346,6 +340,7 @@ __global__ __launch_bounds__(kBlock, chain_waves<MODE>()) void k_episode_chain(
                                  wait_tag, part_prev, n_part_prev, v_prev, b_prev, n_cand,
                                  n_steps, index_base, out_prev, log, cap, epoch);
       } else if constexpr (MODE == kChainFin) {
+        // (this block-0 body has a copy in k_episode_chain_obs, mpc_episode_obs.h: DESIGN.md §5)
         const Consts Kp = S->h.K;
         const EpisodeHook hook{&S->h, log, cap, S->chain_pub, kPubWords, epoch, &S->chain_error};
         // (block 0 never fills the control ring: its LDS holds the re-roll)

@@ -332,6 +332,7 @@ struct CircleObs {
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (NOBS > 4) asm volatile("" : "+s"(t));
 #endif
+    // (FrameObs::loop, mpc_episode_obs.h, has a copy of this loop: DESIGN.md §5)
 #pragma unroll
     for (int i = 0; i < NOBS; ++i) {
       const double cx = t->c[i].cx, cy = t->c[i].cy, r2 = t->c[i].r2;

@@ -2,11 +2,13 @@
 // (mpc_episode_partials_obstacles, mpc_episode_chain_step_obstacles; gfx950).
 //
 //   kernarg_world            the call's world-frame circle table (kernel argument 0)
-//   FrameObs<NOBS>           the lane hook of rect+cum: the table in the frame of
-//                            the sums, formed on the device from the step's pose
-//   k_episode_stream_obs, k_episode_argmin_obs   the streaming / scalar rollout
-//                            of mpc_episode_partials with circles
-//   k_episode_chain_obs      k_episode_chain<kChainFin> with circles
+//   frame_slots, FrameObs<NOBS>   the lane hook of rect+cum: the table in the frame
+//                            of the sums, formed on the device from the step's
+//                            pose (its loop repeats CircleObs::test's, mpc_device.h)
+//   episode_obs_body, k_episode_stream_obs, k_episode_argmin_obs   the streaming /
+//                            scalar rollout of mpc_episode_partials with circles
+//   chain_obs_waves, k_episode_chain_obs   k_episode_chain<kChainFin> with circles
+//                            (block 0: a copy of that kernel's, mpc_chain.h)
 //
 // The world-frame modes (qk21, rect, +rot) test the kernel-argument table as
 // the one-shot kernels do (CircleObs).  rect+cum accumulates sums that know no
@@ -94,6 +96,7 @@ struct FrameObs {
 #else
     [[maybe_unused]] const Circle* t = nullptr;
 #endif
+    // (a copy of CircleObs::test's loop, mpc_device.h: DESIGN.md §5)
 #pragma unroll
     for (int i = 0; i < NOBS; ++i) {
       double cx, cy, r2;
@@ -174,6 +177,7 @@ __global__ __launch_bounds__(kBlock, chain_obs_waves<NOBS>()) void k_episode_cha
     mpc_episode_log_t* __restrict__ log, int cap, unsigned long long* __restrict__ n_blocked) {
   constexpr int INTEG = MPC_INTEG_RECT, ROT = kRotCum;
   if (blockIdx.x == 0) {
+    // (a copy of k_episode_chain's kChainFin block-0 body, mpc_chain.h: DESIGN.md §5)
     if (has_prev) {
       const Consts Kp = S->h.K;
       const EpisodeHook hook{&S->h, log, cap, S->chain_pub, kPubWords, epoch, &S->chain_error};
@@ -184,7 +188,7 @@ __global__ __launch_bounds__(kBlock, chain_obs_waves<NOBS>()) void k_episode_cha
     } else {
       chain_publish(S, epoch);
     }
-    if (threadIdx.x == 0 && (S->h.K.L_pow2 != 0) != PL2) S->chain_error = 2u;   // as k_episode_chain
+    if (threadIdx.x == 0 && (S->h.K.L_pow2 != 0) != PL2) S->chain_error = 2u;
     return;
   }
   chain_tiles<INTEG, ROT, PL2, false, kChainWaitTicks, TILED>(

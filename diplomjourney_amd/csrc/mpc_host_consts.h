@@ -7,6 +7,7 @@
 //   host_consts          Consts of a problem with the reference's libm calls
 //   host_window_consts   Consts of a quad window alone (the full tree's shared
 //                        control table, mpc_fulltree_argmin_batched)
+//   world_obstacles, frame_obstacles   the keep-out circle tables of a call
 // (The device's own derivation, x*x and sincos_fast, is consts_from_problem in
 // mpc_device.h.)
 #pragma once
@@ -69,6 +70,25 @@ inline Consts host_window_consts(double L, double t_a, double t_b) {
   q.t_a = t_a;
   q.t_b = t_b;
   return host_consts(q);
+}
+
+// The circle tables of a call (mpc_device.h Obstacles), one-shot and episode
+// entries alike.  world_obstacles: (x, y, r^2) in world coordinates; entries
+// past n can never be entered (r2 = -1).
+inline Obstacles world_obstacles(const mpc_obstacle_t* obs, int n) {
+  Obstacles W;
+  for (int i = 0; i < MPC_MAX_OBSTACLES; ++i) W.c[i] = Circle{0.0, 0.0, -1.0, 0.0};
+  for (int i = 0; i < n; ++i) W.c[i] = Circle{obs[i].x, obs[i].y, obs[i].r * obs[i].r, 0.0};
+  return W;
+}
+
+// frame_obstacles: the `loop` table of rect+cum for the step that starts at
+// K's pose, frame_circle per entry (the episode kernels form the same table on
+// the device from the state's pose, mpc_episode_obs.h).
+inline Obstacles frame_obstacles(const Consts& K, const Obstacles& world, int n) {
+  Obstacles F = world;
+  for (int i = 0; i < n; ++i) F.c[i] = frame_circle(K, world.c[i], K.L_pow2 != 0);
+  return F;
 }
 
 }  // namespace mpc

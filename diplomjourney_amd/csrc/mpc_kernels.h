@@ -6,7 +6,9 @@
 //                      (cost, index) arg-min (mpc_argmin.h); one 16-B record
 //                      per block.  k_rollout_argmin_stream: the aligned path.
 //   k_rollout_argmin_obs / _stream_obs   the same with keep-out circles
-//                      (kernarg_obs, blocked_slots).
+//                      (kernarg_obs); blocked_slots, store_wave_blocked,
+//                      add_block_blocked: the blocked-count epilogue, also of
+//                      the episode kernels (mpc_chain.h, mpc_episode_obs.h).
 //   k_stream_probe     the streaming kernel's memory side alone.
 //   k_rollout_argmin_batched / k_finalize_batched   robot-segmented variant.
 //   select_index, k_select_winner   lexicographic min over gathered per-rank results.
@@ -28,18 +30,33 @@
 
 namespace mpc {
 
-// The waves' blocked-candidate counts of the obstacle variants (LDS only in
-// the kernels that call this).
+// The waves' blocked-candidate counts of the obstacle variants, one-shot and
+// episode (LDS only in the kernels that call this).
 __device__ __forceinline__ uint32_t* blocked_slots() {
   __shared__ uint32_t s_blocked[kWaves];
   return s_blocked;
 }
 
+// The blocked-count epilogue, in two halves around block_argmin (whose barrier
+// orders the stores before thread 0's reads): every wave stores its uniform
+// count; thread 0 adds the block's sum to n_blocked (nullable), one atomic.
+__device__ __forceinline__ void store_wave_blocked(uint32_t wave_blocked) {
+  if ((threadIdx.x & 63) == 0) blocked_slots()[threadIdx.x >> 6] = wave_blocked;
+}
+__device__ __forceinline__ void add_block_blocked(unsigned long long* __restrict__ n_blocked) {
+  if (threadIdx.x == 0 && n_blocked) {
+    uint32_t total = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) total += blocked_slots()[w];
+    if (total) atomicAdd(n_blocked, static_cast<unsigned long long>(total));
+  }
+}
+
 // Obs::kOn: a blocked candidate takes the key of a non-finite cost (~0: never
 // wins), so the block records and everything downstream of them are those of
 // the kernels without obstacles; n_blocked (nullable) gets the number of
-// blocked candidates — a ballot popcount per wave and candidate slot, one
-// 64-bit atomic add per block.
+// blocked candidates — a ballot popcount per wave and candidate slot, then
+// store_wave_blocked / add_block_blocked.
 template <int CPL, int INTEG, int ROT, bool STATES, bool KDEV, class Obs = NoObs>
 __device__ __forceinline__ void rollout_argmin_body(
     const Consts& Karg, const Consts* __restrict__ Kdev, const double* __restrict__ v,
@@ -72,19 +89,10 @@ __device__ __forceinline__ void rollout_argmin_body(
       }
     }
   }
-  if constexpr (Obs::kOn) {
-    if ((threadIdx.x & 63) == 0) blocked_slots()[threadIdx.x >> 6] = wave_blocked;
-  }   // (block_argmin's barrier orders these stores before thread 0's reads)
+  if constexpr (Obs::kOn) store_wave_blocked(wave_blocked);
   block_argmin<CPL == kCplWide>(best_k, best_i);   // (wide path: rows < 2^28 candidates)
   if (threadIdx.x == 0) part[blockIdx.x] = Rec{best_k, best_i};
-  if constexpr (Obs::kOn) {
-    if (threadIdx.x == 0 && n_blocked) {
-      uint32_t total = 0;
-#pragma unroll
-      for (int w = 0; w < kWaves; ++w) total += blocked_slots()[w];
-      if (total) atomicAdd(n_blocked, static_cast<unsigned long long>(total));
-    }
-  }
+  if constexpr (Obs::kOn) add_block_blocked(n_blocked);
 }
 
 // Scalar (CPL = 1), CoordinateTree-states and register-ring paths.

@@ -251,64 +251,12 @@ int check_obstacles(const mpc_obstacle_t* obs, int32_t n) {
   return MPC_OK;
 }
 
-// The launch's circle tables (mpc_device.h Obstacles): `world` as given;
-// `loop` in the frame of the recurrence's (x, y) — for kRotCum the centres in
-// the start-pose frame, A = c0 dx + s0 dy, B = c0 dy - s0 dx with (dx, dy) the
-// centre minus the start position (the inverse of cum_pose), and for the
-// 1/L-scaled sums (L a power of two) centres and radius times 1/L.  Entries
-// past n can never be entered (r2 = -1).
+// The one-shot launch's circle tables (mpc_host_consts.h): `world` as given;
+// `loop` in the frame of the recurrence's (x, y) — world coordinates, or for
+// kRotCum the start-pose frame of the sums.
 ObstacleArgs host_obstacles(const Consts& K, const mpc_obstacle_t* obs, int n, bool cum) {
-  ObstacleArgs O;
-  for (int i = 0; i < MPC_MAX_OBSTACLES; ++i) O.world.c[i] = Circle{0.0, 0.0, -1.0, 0.0};
-  for (int i = 0; i < n; ++i) O.world.c[i] = Circle{obs[i].x, obs[i].y, obs[i].r * obs[i].r, 0.0};
-  O.loop = O.world;
-  if (cum) {
-    const double sc = K.L_pow2 ? K.inv_L : 1.0;
-    for (int i = 0; i < n; ++i) {
-      const double dx = obs[i].x - K.x, dy = obs[i].y - K.y, r = obs[i].r * sc;
-      O.loop.c[i] = Circle{(K.c0 * dx + K.s0 * dy) * sc, (K.c0 * dy - K.s0 * dx) * sc, r * r, 0.0};
-    }
-  }
-  return O;
-}
-
-// The obstacle variant of launch_rollout / the states launch: the same grid
-// and path choice (so partial_count holds), instantiated for 1, 4 or
-// MPC_MAX_OBSTACLES circles on the streaming path and for MPC_MAX_OBSTACLES on
-// the one-candidate-per-lane paths.
-void launch_rollout_obs(hipStream_t st, int32_t integrator, const Consts& K, const ObstacleArgs& O,
-                        int n_obs, const double* v, const double* b, int64_t n_cand, int n_steps,
-                        Rec* part, double* states, unsigned long long* n_blocked) {
-  const bool wide = !states && wide_ok(v, b, n_cand);
-  dispatch_mode(integrator, [&](auto I, auto R) {
-    constexpr int kAll = MPC_MAX_OBSTACLES;
-    const dim3 g1(static_cast<unsigned>(rollout_grid<1>(n_cand)));
-    const dim3 g2(static_cast<unsigned>(rollout_grid<kCplWide>(n_cand)));
-    if (states)
-      k_rollout_argmin_obs<1, I, R, true, kAll><<<g1, kBlock, 0, st>>>(
-          O, K, v, b, n_cand, n_steps, part, states, n_blocked);
-    else if (!wide)
-      k_rollout_argmin_obs<1, I, R, false, kAll><<<g1, kBlock, 0, st>>>(
-          O, K, v, b, n_cand, n_steps, part, nullptr, n_blocked);
-    else if (n_obs <= 1)
-      k_rollout_argmin_stream_obs<I, R, 1><<<g2, kBlock, 0, st>>>(O, K, v, b, n_cand, n_steps,
-                                                                  part, n_blocked);
-    else if (n_obs <= 4)
-      k_rollout_argmin_stream_obs<I, R, 4><<<g2, kBlock, 0, st>>>(O, K, v, b, n_cand, n_steps,
-                                                                  part, n_blocked);
-    else
-      k_rollout_argmin_stream_obs<I, R, kAll><<<g2, kBlock, 0, st>>>(O, K, v, b, n_cand, n_steps,
-                                                                     part, n_blocked);
-  });
-}
-
-// The episode entries' table: the circles in world coordinates alone (the
-// rect+cum frame table is formed on the device, mpc_episode_obs.h).
-Obstacles world_obstacles(const mpc_obstacle_t* obs, int n) {
-  Obstacles W;
-  for (int i = 0; i < MPC_MAX_OBSTACLES; ++i) W.c[i] = Circle{0.0, 0.0, -1.0, 0.0};
-  for (int i = 0; i < n; ++i) W.c[i] = Circle{obs[i].x, obs[i].y, obs[i].r * obs[i].r, 0.0};
-  return W;
+  const Obstacles W = world_obstacles(obs, n);
+  return ObstacleArgs{cum ? frame_obstacles(K, W, n) : W, W};
 }
 
 // n_obs -> f(IC<NOBS>) over the instantiations: 4 or all, and with ONE also 1.
@@ -323,7 +271,35 @@ void dispatch_nobs(int n_obs, F&& f) {
     f(IC<MPC_MAX_OBSTACLES>{});
 }
 
-// launch_rollout<true> with circles: the same grid and path choice.
+// The obstacle variant of launch_rollout / the states launch: the same grid
+// and path choice (so partial_count holds), instantiated per circle count
+// (dispatch_nobs) on the streaming path and for MPC_MAX_OBSTACLES on the
+// one-candidate-per-lane paths.
+void launch_rollout_obs(hipStream_t st, int32_t integrator, const Consts& K, const ObstacleArgs& O,
+                        int n_obs, const double* v, const double* b, int64_t n_cand, int n_steps,
+                        Rec* part, double* states, unsigned long long* n_blocked) {
+  const bool wide = !states && wide_ok(v, b, n_cand);
+  dispatch_mode(integrator, [&](auto I, auto R) {
+    constexpr int kAll = MPC_MAX_OBSTACLES;
+    const dim3 g1(static_cast<unsigned>(rollout_grid<1>(n_cand)));
+    const dim3 g2(static_cast<unsigned>(rollout_grid<kCplWide>(n_cand)));
+    if (states)
+      k_rollout_argmin_obs<1, I, R, true, kAll><<<g1, kBlock, 0, st>>>(
+          O, K, v, b, n_cand, n_steps, part, states, n_blocked);
+    else if (!wide)
+      k_rollout_argmin_obs<1, I, R, false, kAll><<<g1, kBlock, 0, st>>>(
+          O, K, v, b, n_cand, n_steps, part, nullptr, n_blocked);
+    else
+      dispatch_nobs<true>(n_obs, [&](auto NOBS) {
+        k_rollout_argmin_stream_obs<I, R, NOBS><<<g2, kBlock, 0, st>>>(O, K, v, b, n_cand, n_steps,
+                                                                       part, n_blocked);
+      });
+  });
+}
+
+// launch_rollout<true> with circles (the episode entries: the world table
+// alone, the rect+cum frame table is formed on the device, mpc_episode_obs.h):
+// the same grid and path choice.
 void launch_episode_obs(hipStream_t st, int32_t integrator, const Obstacles& W, int n_obs,
                         const Consts* Kdev, const double* v, const double* b, int64_t n_cand,
                         int n_steps, Rec* part, unsigned long long* n_blocked) {
@@ -457,6 +433,72 @@ EpisodeHook episode_hook(EpisodeState* S, bool advance, mpc_episode_log_t* log,
                          int32_t log_capacity) {
   return EpisodeHook{advance ? &S->h : nullptr, log, log_capacity,
                      advance ? S->chain_pub : nullptr, advance ? kPubWords : 0};
+}
+
+// mpc_episode_partials (no circles, no count) and mpc_episode_partials_obstacles:
+// the circles are checked first, the count is zeroed once every check has
+// passed, and with no circles the plain kernels run (nothing can be blocked).
+int episode_partials(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                     const double* v_sc, const double* beta_sc, int64_t n_cand, int32_t n_steps,
+                     int32_t integrator, void* ws, size_t ws_bytes, int64_t* n_blocked_out,
+                     mpc_stream_t stream) {
+  if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
+  if (check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK) return MPC_ERR_ARG;
+  if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
+  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (zero_blocked(n_blocked_out, st) != MPC_OK) return MPC_ERR_HIP;
+  EpisodeState* S = static_cast<EpisodeState*>(state);
+  if (n_obstacles == 0)
+    launch_rollout<true>(st, integrator, Consts{}, &S->h.K, v_sc, beta_sc, n_cand, n_steps,
+                         static_cast<Rec*>(ws));
+  else
+    launch_episode_obs(st, integrator, world_obstacles(obstacles, n_obstacles), n_obstacles,
+                       &S->h.K, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws),
+                       reinterpret_cast<unsigned long long*>(n_blocked_out));
+  return last_hip_status();
+}
+
+// mpc_episode_chain_step and mpc_episode_chain_step_obstacles, in the same way.
+int episode_chain_step(const mpc_episode_config_t* cfg, void* state,
+                       const mpc_obstacle_t* obstacles, int32_t n_obstacles, int32_t mode,
+                       uint32_t epoch, const double* v_sc, const double* beta_sc, int64_t n_cand,
+                       int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
+                       const void* ws_prev, size_t ws_bytes, const double* v_prev,
+                       const double* beta_prev, mpc_result_t* out_prev, mpc_episode_log_t* log,
+                       int32_t log_capacity, int64_t* n_blocked_out, mpc_stream_t stream) {
+  if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
+  int has_prev = 0;
+  const int a = check_chain_step(cfg, state, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
+                                 index_base, integrator, ws, ws_prev, ws_bytes, v_prev, beta_prev,
+                                 out_prev, log_capacity, &has_prev);
+  if (a != MPC_OK) return a;
+  EpisodeState* S = static_cast<EpisodeState*>(state);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (zero_blocked(n_blocked_out, st) != MPC_OK) return MPC_ERR_HIP;
+  // block 0 + one block per tile; the previous step's records are as many
+  // (same n_cand), and as many as mpc_episode_finalize reduces
+  const int64_t tiles = rollout_grid<kCplWide>(n_cand);
+  const int n_part_prev = static_cast<int>(tiles);
+  Rec* part = static_cast<Rec*>(ws);
+  const Rec* part_prev = static_cast<const Rec*>(ws_prev);
+  dispatch_bools(
+      [&](auto PL2, auto TILED) {
+        if (n_obstacles == 0)
+          k_episode_chain<MPC_INTEG_RECT, kRotCum, kChainFin, PL2, TILED>
+              <<<tiles + 1, kBlock, 0, st>>>(
+                  S, epoch, v_sc, beta_sc, n_cand, n_steps, part, has_prev, part_prev, n_part_prev,
+                  v_prev, beta_prev, index_base, out_prev, nullptr, 0, *cfg, log, log_capacity, 0u);
+        else
+          dispatch_nobs<false>(n_obstacles, [&](auto NOBS) {
+            k_episode_chain_obs<PL2, TILED, NOBS><<<tiles + 1, kBlock, 0, st>>>(
+                world_obstacles(obstacles, n_obstacles), S, epoch, v_sc, beta_sc, n_cand, n_steps,
+                part, has_prev, part_prev, n_part_prev, v_prev, beta_prev, index_base, out_prev,
+                *cfg, log, log_capacity, reinterpret_cast<unsigned long long*>(n_blocked_out));
+          });
+      },
+      length_pow2(cfg->L), is_tiled(integrator));
+  return last_hip_status();
 }
 
 }  // namespace
@@ -802,13 +844,8 @@ int mpc_episode_generate_step(const mpc_episode_config_t* cfg, void* state, int6
 int mpc_episode_partials(void* state, const double* v_sc, const double* beta_sc, int64_t n_cand,
                          int32_t n_steps, int32_t integrator, void* ws, size_t ws_bytes,
                          mpc_stream_t stream) {
-  if (check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK) return MPC_ERR_ARG;
-  if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
-  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
-  EpisodeState* S = static_cast<EpisodeState*>(state);
-  launch_rollout<true>(reinterpret_cast<hipStream_t>(stream), integrator, Consts{}, &S->h.K, v_sc,
-                       beta_sc, n_cand, n_steps, static_cast<Rec*>(ws));
-  return last_hip_status();
+  return episode_partials(state, nullptr, 0, v_sc, beta_sc, n_cand, n_steps, integrator, ws,
+                          ws_bytes, nullptr, stream);
 }
 
 int mpc_episode_finalize(void* state, const double* v_sc, const double* beta_sc, int64_t n_cand,
@@ -847,20 +884,8 @@ int mpc_episode_partials_obstacles(void* state, const mpc_obstacle_t* obstacles,
                                    const double* beta_sc, int64_t n_cand, int32_t n_steps,
                                    int32_t integrator, void* ws, size_t ws_bytes,
                                    int64_t* n_blocked_out, mpc_stream_t stream) {
-  if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
-  if (check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK) return MPC_ERR_ARG;
-  if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
-  if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (zero_blocked(n_blocked_out, st) != MPC_OK) return MPC_ERR_HIP;
-  if (n_obstacles == 0)   // the kernels without obstacles: nothing can be blocked
-    return mpc_episode_partials(state, v_sc, beta_sc, n_cand, n_steps, integrator, ws, ws_bytes,
-                                stream);
-  EpisodeState* S = static_cast<EpisodeState*>(state);
-  launch_episode_obs(st, integrator, world_obstacles(obstacles, n_obstacles), n_obstacles,
-                     &S->h.K, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws),
-                     reinterpret_cast<unsigned long long*>(n_blocked_out));
-  return last_hip_status();
+  return episode_partials(state, obstacles, n_obstacles, v_sc, beta_sc, n_cand, n_steps,
+                          integrator, ws, ws_bytes, n_blocked_out, stream);
 }
 
 int mpc_episode_step_obstacles(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
@@ -905,35 +930,14 @@ int mpc_episode_rollout(void* state, const double* v_sc, const double* beta_sc, 
 
 int mpc_episode_chain_step(const mpc_episode_config_t* cfg, void* state, int32_t mode,
                            uint32_t epoch, const double* v_sc, const double* beta_sc,
-                           int64_t n_cand,
-                           int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
-                           const void* ws_prev, size_t ws_bytes, const double* v_prev,
-                           const double* beta_prev, mpc_result_t* out_prev,
-                           const mpc_result_t* gathered, int32_t n_gathered,
+                           int64_t n_cand, int32_t n_steps, int64_t index_base,
+                           int32_t integrator, void* ws, const void* ws_prev, size_t ws_bytes,
+                           const double* v_prev, const double* beta_prev, mpc_result_t* out_prev,
+                           const mpc_result_t* /*gathered*/, int32_t /*n_gathered*/,
                            mpc_episode_log_t* log, int32_t log_capacity, mpc_stream_t stream) {
-  (void)gathered;
-  (void)n_gathered;
-  int has_prev = 0;
-  const int a = check_chain_step(cfg, state, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
-                                 index_base, integrator, ws, ws_prev, ws_bytes, v_prev, beta_prev,
-                                 out_prev, log_capacity, &has_prev);
-  if (a != MPC_OK) return a;
-  EpisodeState* S = static_cast<EpisodeState*>(state);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // block 0 + one block per tile; the previous step's records are as many
-  // (same n_cand), and as many as mpc_episode_finalize reduces
-  const int64_t tiles = rollout_grid<kCplWide>(n_cand);
-  const int n_part_prev = static_cast<int>(tiles);
-  dispatch_bools(
-      [&](auto PL2, auto TILED) {
-        k_episode_chain<MPC_INTEG_RECT, kRotCum, kChainFin, PL2, TILED>
-            <<<tiles + 1, kBlock, 0, st>>>(
-                S, epoch, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws), has_prev,
-                static_cast<const Rec*>(ws_prev), n_part_prev, v_prev, beta_prev, index_base,
-                out_prev, nullptr, 0, *cfg, log, log_capacity, 0u);
-      },
-      length_pow2(cfg->L), is_tiled(integrator));
-  return last_hip_status();
+  return episode_chain_step(cfg, state, nullptr, 0, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
+                            index_base, integrator, ws, ws_prev, ws_bytes, v_prev, beta_prev,
+                            out_prev, log, log_capacity, nullptr, stream);
 }
 
 int mpc_episode_chain_step_obstacles(
@@ -941,35 +945,11 @@ int mpc_episode_chain_step_obstacles(
     int32_t n_obstacles, int32_t mode, uint32_t epoch, const double* v_sc, const double* beta_sc,
     int64_t n_cand, int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
     const void* ws_prev, size_t ws_bytes, const double* v_prev, const double* beta_prev,
-    mpc_result_t* out_prev, const mpc_result_t* gathered, int32_t n_gathered,
+    mpc_result_t* out_prev, const mpc_result_t* /*gathered*/, int32_t /*n_gathered*/,
     mpc_episode_log_t* log, int32_t log_capacity, int64_t* n_blocked_out, mpc_stream_t stream) {
-  if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
-  int has_prev = 0;
-  const int a = check_chain_step(cfg, state, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
-                                 index_base, integrator, ws, ws_prev, ws_bytes, v_prev, beta_prev,
-                                 out_prev, log_capacity, &has_prev);
-  if (a != MPC_OK) return a;
-  EpisodeState* S = static_cast<EpisodeState*>(state);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (zero_blocked(n_blocked_out, st) != MPC_OK) return MPC_ERR_HIP;
-  if (n_obstacles == 0)   // the base entry: the same kernels, nothing can be blocked
-    return mpc_episode_chain_step(cfg, state, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
-                                  index_base, integrator, ws, ws_prev, ws_bytes, v_prev, beta_prev,
-                                  out_prev, gathered, n_gathered, log, log_capacity, stream);
-  const Obstacles W = world_obstacles(obstacles, n_obstacles);
-  const int64_t tiles = rollout_grid<kCplWide>(n_cand);
-  dispatch_bools(
-      [&](auto PL2, auto TILED) {
-        dispatch_nobs<false>(n_obstacles, [&](auto NOBS) {
-          k_episode_chain_obs<PL2, TILED, NOBS><<<tiles + 1, kBlock, 0, st>>>(
-              W, S, epoch, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws), has_prev,
-              static_cast<const Rec*>(ws_prev), static_cast<int>(tiles), v_prev, beta_prev,
-              index_base, out_prev, *cfg, log, log_capacity,
-              reinterpret_cast<unsigned long long*>(n_blocked_out));
-        });
-      },
-      length_pow2(cfg->L), is_tiled(integrator));
-  return last_hip_status();
+  return episode_chain_step(cfg, state, obstacles, n_obstacles, mode, epoch, v_sc, beta_sc, n_cand,
+                            n_steps, index_base, integrator, ws, ws_prev, ws_bytes, v_prev,
+                            beta_prev, out_prev, log, log_capacity, n_blocked_out, stream);
 }
 
 #ifdef MPC_RUN_STATS

@@ -46,12 +46,7 @@ class _OneGpuChain(_ChainForm):
         ws, ws_prev = ep._ws
         args = (1, ep._next_epoch(), vp, bp, *ep._shard, integ, ws.data_ptr(),
                 ws_prev.data_ptr(), ws.numel(), *ep._prev_ptrs(pend), ep.local.data_ptr(), None, 0)
-        if ep._n_obs or ep._obstacle_entries:
-            log, cap, st = ep._tail()
-            ep._C.mpc_episode_chain_step_obstacles(*ep._head, *ep._circles(), *args, log, cap,
-                                                   ep._blocked_ptr(), st)
-        else:
-            ep._C.mpc_episode_chain_step(*ep._head, *args, *ep._tail())
+        ep._entry("mpc_episode_chain_step", ep._head, *args, *ep._tail())
         _stop(events)
         return ctl
 
@@ -336,10 +331,6 @@ class DeviceEpisode:
         self.steps_enqueued = 0
         self.n_blocked = torch.zeros(1, dtype=torch.int64, device=dev)
         self._obs, self._n_obs = None, 0
-        # (tools/episode_obstacle_cost.py: take the obstacle entries with no
-        # circles too, to time their dispatch of the plain kernels)
-        self._obstacle_entries = False
-        self._count_blocked = True      # (the same tool: n_blocked's memset costs ~5 us a step)
         self.set_obstacles(obstacles)
         self.reset(_fresh_mailbox=True)
 
@@ -362,11 +353,23 @@ class DeviceEpisode:
     def _takes_obstacles(self):
         return self.split and not self.generate and not (self.chain and self.exchange)
 
-    def _blocked_ptr(self):
-        return self.n_blocked.data_ptr() if self._count_blocked else None
+    def _obstacle_args(self):
+        """The hook of _entry: None (the base entries), or what their _obstacles
+        twins take besides: (circles, count, n_blocked_out)."""
+        if not self._n_obs:
+            return None
+        return self._obs, self._n_obs, self.n_blocked.data_ptr()
 
-    def _circles(self):
-        return self._obs, self._n_obs
+    def _entry(self, name, head, *args):
+        """The call site of the chained launch, the two-launch step and partials:
+        entry `name`, or with circles its `_obstacles` twin, which takes them
+        after `head` (up to the state) and n_blocked_out before the stream."""
+        extra = self._obstacle_args()
+        if extra is None:
+            return getattr(self._C, name)(*head, *args)
+        *circles, blocked = extra
+        twin = getattr(self._C, name + "_obstacles")
+        return twin(*head, *circles, *args[:-1], blocked, args[-1])
 
     def _p2p_setup(self, dev, uncached):
         """The mailbox's three stages (_Mailbox), the ranks' verdict reduced
@@ -617,16 +620,12 @@ class DeviceEpisode:
                 self.log.data_ptr() if one_gpu else None, self.log_capacity if one_gpu else 0, st)
         if events:
             events[0].record()
-        if (self._n_obs or self._obstacle_entries) and not events:
-            # (split, checked by set_obstacles) the same two launches, the
-            # rollout with circles
-            C.mpc_episode_step_obstacles(args[0], *self._circles(), *args[1:-1],
-                                         self._blocked_ptr(), st)
-        elif self.split and not events:
+        if self.split and not events:
             # streaming kernel, then the selection kernel: two launches in one
             # host call (the faster form on MI355X: 44.8 vs 47.5 us per
-            # config-C step than the one-launch form below)
-            C.mpc_episode_step(*args)
+            # config-C step than the one-launch form below); with circles
+            # (split, checked by set_obstacles) the rollout tests them
+            self._entry("mpc_episode_step", args[:1], *args[1:])
         elif self.split:
             self.partials(st)
             C.mpc_episode_finalize(*args)
@@ -645,15 +644,8 @@ class DeviceEpisode:
             raise ValueError("the streaming kernel alone reads SoA controls")
         v, b = self.cur
         st = st if st is not None else native.current_stream()
-        if self._n_obs or self._obstacle_entries:
-            self._C.mpc_episode_partials_obstacles(
-                self.state.data_ptr(), *self._circles(), v.data_ptr(), b.data_ptr(), self.n_local,
-                self.n_steps, self._integ, self.ws.data_ptr(), self.ws.numel(),
-                self._blocked_ptr(), st)
-            return
-        self._C.mpc_episode_partials(
-            self.state.data_ptr(), v.data_ptr(), b.data_ptr(), self.n_local,
-            self.n_steps, self._integ, self.ws.data_ptr(), self.ws.numel(), st)
+        self._entry("mpc_episode_partials", (self.state.data_ptr(),), v.data_ptr(), b.data_ptr(),
+                    self.n_local, self.n_steps, self._integ, self.ws.data_ptr(), self.ws.numel(), st)
 
     def advance(self):
         """Multi-GPU: all_gather of the per-rank winners (RCCL) + selection +

@@ -64,6 +64,16 @@ class Expansion:
         return self._ws
 
     # -- single problem --------------------------------------------------------
+    def _one_shot(self, name, problem, obstacles, n_blocked, args, tail):
+        """Entry `name`, or with obstacles / n_blocked its `_obstacles` twin: the
+        circles after the problem, n_blocked_out before `tail`."""
+        obs, n_obs = make_obstacles(obstacles)
+        if n_obs or n_blocked is not None:
+            getattr(self._C, name + "_obstacles")(ctypes.byref(problem), obs, n_obs, *args,
+                                                  _blocked_ptr(n_blocked), *tail)
+        else:
+            getattr(self._C, name)(ctypes.byref(problem), *args, *tail)
+
     def rollout_argmin(self, problem: MpcProblem, v_sc, beta_sc, index_base=0,
                        incumbent=math.inf, integrator="qk21", states=None, out=None,
                        obstacles=None, n_blocked=None):
@@ -89,20 +99,11 @@ class Expansion:
         out = self.result if out is None else out
         ws_bytes = self.lib.mpc_workspace_bytes(n_cand, n_steps)
         ws = self._workspace(ws_bytes)
-        obs, n_obs = make_obstacles(obstacles)
-        if n_obs or n_blocked is not None:
-            self._C.mpc_rollout_argmin_obstacles(
-                ctypes.byref(problem), obs, n_obs, v_sc.data_ptr(), beta_sc.data_ptr(), n_cand,
-                n_steps, int(index_base), float(incumbent), _integ(integrator),
-                states.data_ptr() if states is not None else None,
-                ws.data_ptr(), ws.numel(), _blocked_ptr(n_blocked), out.data_ptr(),
-                native.current_stream())
-            return out
-        self._C.mpc_rollout_argmin(
-            ctypes.byref(problem), v_sc.data_ptr(), beta_sc.data_ptr(), n_cand, n_steps,
-            int(index_base), float(incumbent), _integ(integrator),
-            states.data_ptr() if states is not None else None,
-            ws.data_ptr(), ws.numel(), out.data_ptr(), native.current_stream())
+        self._one_shot("mpc_rollout_argmin", problem, obstacles, n_blocked,
+                       (v_sc.data_ptr(), beta_sc.data_ptr(), n_cand, n_steps, int(index_base),
+                        float(incumbent), _integ(integrator),
+                        states.data_ptr() if states is not None else None, ws.data_ptr(),
+                        ws.numel()), (out.data_ptr(), native.current_stream()))
         return out
 
     def partials(self, problem: MpcProblem, v_sc, beta_sc, integrator="qk21", obstacles=None,
@@ -111,16 +112,9 @@ class Expansion:
         obstacles / n_blocked: as in rollout_argmin (mpc_rollout_partials_obstacles)."""
         n_steps, n_cand = v_sc.shape
         ws = self._workspace(self.lib.mpc_workspace_bytes(n_cand, n_steps))
-        obs, n_obs = make_obstacles(obstacles)
-        if n_obs or n_blocked is not None:
-            self._C.mpc_rollout_partials_obstacles(
-                ctypes.byref(problem), obs, n_obs, v_sc.data_ptr(), beta_sc.data_ptr(), n_cand,
-                n_steps, _integ(integrator), None, ws.data_ptr(), ws.numel(),
-                _blocked_ptr(n_blocked), native.current_stream())
-            return
-        self._C.mpc_rollout_partials(ctypes.byref(problem), v_sc.data_ptr(), beta_sc.data_ptr(),
-                                     n_cand, n_steps, _integ(integrator), None, ws.data_ptr(),
-                                     ws.numel(), native.current_stream())
+        self._one_shot("mpc_rollout_partials", problem, obstacles, n_blocked,
+                       (v_sc.data_ptr(), beta_sc.data_ptr(), n_cand, n_steps, _integ(integrator),
+                        None, ws.data_ptr(), ws.numel()), (native.current_stream(),))
 
     def finalize(self, problem: MpcProblem, v_sc, beta_sc, index_base=0, incumbent=math.inf,
                  integrator="qk21", out=None):

@@ -164,7 +164,10 @@ int mpc_rollout_finalize(const mpc_problem_t* p, const double* v_sc, const doubl
  *     state after step k satisfies (x_k - x)^2 + (y_k - y)^2 < r^2.  The start
  *     pose is not tested (a robot that starts inside can leave), and only
  *     step-end states are: the caller inflates r for the robot's size and for
- *     the distance covered in one step.
+ *     the distance covered in one step.  In MPC_HEADING_CUMULATIVE mode with L
+ *     a power of two the test runs on sums scaled by 1/L, against r^2 * (1/L)^2
+ *     in the one-shot and the episode entries alike: equal to (r / L)^2 unless
+ *     either square is subnormal (r below about 1e-154 * L).
  *   - A blocked candidate never wins, whatever its cost.  If every candidate
  *     is blocked the result is the "no finite cost" result: index -1, found 0.
  *   - Ties and the incumbent test are those of mpc_rollout_argmin.  A NaN

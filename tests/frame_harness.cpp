@@ -1,7 +1,8 @@
 // Host build of frame_circle (csrc/mpc_device.h): the rect+cum circle table of
-// the device-resident episode steps, as the kernels form it, for
+// the device-resident episode steps, as the kernels form it, and the library's
+// own table builder (csrc/mpc_host_consts.h), for
 // tests/test_episode_obstacles_abi.py.
-#include "../diplomjourney_amd/csrc/mpc_device.h"
+#include "../diplomjourney_amd/csrc/mpc_host_consts.h"
 
 using namespace mpc;
 
@@ -31,6 +32,19 @@ void frame_circles(const mpc_problem_t* p, const double* world, int n, double* o
     out[3 * i] = f.cx;
     out[3 * i + 1] = f.cy;
     out[3 * i + 2] = f.r2;
+  }
+}
+
+// world_obstacles / frame_obstacles, the builder the entries call: n circles
+// (x, y, r) -> all MPC_MAX_OBSTACLES entries (cx, cy, r2) of the world table and
+// of the rect+cum loop table of the step that starts at p's pose.
+void frame_tables(const mpc_problem_t* p, const mpc_obstacle_t* circles, int n, double* world,
+                  double* loop) {
+  const Consts K = consts_from_problem(*p);
+  const Obstacles W = world_obstacles(circles, n), F = frame_obstacles(K, W, n);
+  for (int i = 0; i < MPC_MAX_OBSTACLES; ++i) {
+    const double w[3] = {W.c[i].cx, W.c[i].cy, W.c[i].r2}, f[3] = {F.c[i].cx, F.c[i].cy, F.c[i].r2};
+    for (int q = 0; q < 3; ++q) world[3 * i + q] = w[q], loop[3 * i + q] = f[q];
   }
 }
 

@@ -3,14 +3,15 @@
 per-candidate costs and [N, 3, C] states: the blocked mask is formed from those
 states in numpy with the header's formula, and the expected winner is the lowest
 (cost, index) among the unblocked candidates.  A case is computed once and shared
-(read-only arrays)."""
+(read-only arrays).  rejected_circles(): the circle arguments every obstacle
+entry refuses (tests/test_obstacles_abi.py, tests/test_episode_obstacles_abi.py)."""
 import functools
 import math
 from types import SimpleNamespace
 
 import numpy as np
 
-from diplomjourney_amd.abi import make_problem
+from diplomjourney_amd.abi import MPC_MAX_OBSTACLES, MpcObstacle, make_problem
 
 POSE = (0.0, 0.0, 0.3)
 V_GRID = np.linspace(0.2, 0.95, 16)
@@ -24,6 +25,28 @@ MODES = tuple(ORACLE_OF)
 # both oracles (a seed that misses one is replaced, never the bound).
 SEED = 1
 MARGIN = 1e-9
+
+
+def rejected_circles():
+    """{what: (mpc_obstacle_t array or None, n_obstacles)}: every circle argument
+    an obstacle entry answers with MPC_ERR_ARG before it looks at anything else
+    — a count out of range, no array, and each unacceptable circle both alone
+    and behind an acceptable one."""
+    def circles(*rows):
+        return (MpcObstacle * len(rows))(*[MpcObstacle(*r) for r in rows])
+
+    ok = (1.0, 2.0, 0.5)
+    bad = {"negative count": (circles(ok), -1),
+           "too many": (circles(*[(float(i), 0.0, 0.1) for i in range(MPC_MAX_OBSTACLES + 1)]),
+                        MPC_MAX_OBSTACLES + 1),
+           "no array": (None, 1)}
+    for what, row in (("nan centre", (math.nan, 0.0, 1.0)), ("inf centre", (0.0, math.inf, 1.0)),
+                      ("-inf centre", (-math.inf, 0.0, 1.0)), ("nan radius", (0.0, 0.0, math.nan)),
+                      ("inf radius", (0.0, 0.0, math.inf)), ("zero radius", (0.0, 0.0, 0.0)),
+                      ("negative radius", (0.0, 0.0, -1.0))):
+        bad[what] = (circles(row), 1)
+        bad[what + " after a valid circle"] = (circles(ok, row), 2)
+    return bad
 
 
 def problem():

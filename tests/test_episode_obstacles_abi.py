@@ -12,6 +12,7 @@ import pytest
 
 import episode_obstacle_cases as EC
 import harness
+import obstacle_cases
 import ranking as R
 from diplomjourney_amd import abi, native
 
@@ -85,18 +86,8 @@ def test_obstacle_rejections_without_gpu():
     """Every obstacle rejection is MPC_ERR_ARG with otherwise acceptable
     arguments (fake pointers: a call that got past the check would fault or
     report a HIP error), also when the base arguments are wrong as well."""
-    one = [(1.0, 2.0, 0.5)]
-    bad = {
-        "negative count": (_circles(one)[0], -1),
-        "too many": ((abi.MpcObstacle * 17)(*[abi.MpcObstacle(1.0, 2.0, 0.5)] * 17), 17),
-        "no array": (None, 1),
-        "nan centre": _circles([(math.nan, 0.0, 1.0)]),
-        "inf centre": _circles([(0.0, math.inf, 1.0)]),
-        "inf radius": _circles([(0.0, 0.0, math.inf)]),
-        "nan radius": _circles([(0.0, 0.0, math.nan)]),
-        "zero radius": _circles([(0.0, 0.0, 0.0)]),
-        "negative radius": _circles(one + [(0.0, 0.0, -1.0)]),
-    }
+    bad = obstacle_cases.rejected_circles()
+    assert len(bad) == 17
     for name, call in _calls().items():
         for what, obs in bad.items():
             assert call(obs) == abi.MPC_ERR_ARG, (name, what)
@@ -147,15 +138,32 @@ def _frame_lib():
     L.frame_consts.argtypes = [ctypes.POINTER(abi.MpcProblem), _P]
     L.frame_circles.argtypes = [ctypes.POINTER(abi.MpcProblem), _P, ctypes.c_int, _P]
     L.frame_cum_pose.argtypes = [ctypes.POINTER(abi.MpcProblem), _P, ctypes.c_int, _P]
+    L.frame_tables.argtypes = [ctypes.POINTER(abi.MpcProblem), _P, ctypes.c_int, _P, _P]
     return L
+
+
+def _tables(lib, p, circles):
+    """The library's own builder (world_obstacles / frame_obstacles,
+    csrc/mpc_host_consts.h) on the rows (x, y, r): the world and the rect+cum
+    loop table, all 16 entries (cx, cy, r2) of each."""
+    obs, n = abi.make_obstacles([tuple(c) for c in circles])
+    world, loop = np.full((16, 3), np.nan), np.full((16, 3), np.nan)
+    lib.frame_tables(ctypes.byref(p), obs, n, world.ctypes.data_as(_P), loop.ctypes.data_as(_P))
+    return world, loop
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 @pytest.mark.parametrize("L", R.WHEELBASES)
 def test_frame_circle_on_the_host(L):
     """frame_circle (csrc/mpc_device.h), the table the rect+cum kernels form
-    from the episode's pose: its numbers are host_obstacles's formula, and a
-    point of the sums frame is inside the transformed circle exactly when its
-    cum_pose is inside the world circle."""
+    from the episode's pose: its numbers are the frame formula's, the tables
+    the library's builder makes (frame_obstacles, the one-shot entries' `loop`
+    table) are that formula on the bits, padding included, and a point of the
+    sums frame is inside the transformed circle exactly when its cum_pose is
+    inside the world circle."""
     lib = _frame_lib()
     rng = np.random.default_rng(20261020)
     headings = (0.7, 2.3, -2.4, -0.6, 3.9, 5.8, 0.0, math.pi / 2)   # every quadrant
@@ -171,12 +179,22 @@ def test_frame_circle_on_the_host(L):
                                  rng.uniform(0.02, 0.6, 16)])
         got = np.zeros((16, 3))
         lib.frame_circles(ctypes.byref(p), world.ctypes.data_as(_P), 16, got.ctypes.data_as(_P))
-        # host_obstacles (csrc/mpc_rollout.hip), operation for operation
+        # the frame formula, operation for operation
         sc = inv_L if pow2 else 1.0
+        wants = []
         for (wx, wy, wr), g in zip(world.tolist(), got.tolist()):
             dx, dy, r = wx - x0, wy - y0, wr * sc
             want = [(c0 * dx + s0 * dy) * sc, (c0 * dy - s0 * dx) * sc, r * r]
             assert g == want, (k, g, want)
+            wants.append(want)
+        # the tables the entries launch with: that formula, the world circles
+        # as given and r2 = -1 past the count, on the bits
+        for n in (0, 1, 4, 5, 16):
+            tw, tl = _tables(lib, p, world[:n])
+            pad = [[0.0, 0.0, -1.0]] * (16 - n)
+            want_w = [[wx, wy, wr * wr] for wx, wy, wr in world[:n].tolist()] + pad
+            assert (_bits(tw) == _bits(want_w)).all(), (k, n)
+            assert (_bits(tl) == _bits(wants[:n] + pad)).all(), (k, n)
         # points of the sums frame around every circle: near its rim and anywhere
         for (wx, wy, wr), (cx, cy, r2) in zip(world.tolist(), got.tolist()):
             m = 400
@@ -196,6 +214,29 @@ def test_frame_circle_on_the_host(L):
             n_in += int((inside_world & clear).sum())
             n_out += int((~inside_world & clear).sum())
     assert n_in > 1000 and n_out > 1000
+
+
+def test_frame_radius_is_the_scaled_radius_squared():
+    """frame_obstacles forms r2 as r^2 * sc^2 (frame_circle), the one-shot
+    entries formed (r * sc)^2 before they shared it: the same bits for every
+    radius whose squares are normal numbers (include/mpc_rollout.h), with the
+    scale of a power-of-two wheelbase (1/L) and without one."""
+    lib = _frame_lib()
+    rng = np.random.default_rng(20261020)
+    radii = np.concatenate([np.logspace(-140, 140, 60), rng.uniform(0.02, 0.6, 16)])
+    for L in R.WHEELBASES + (0.3, 4.0):      # 0.45, 0.3: no scale; 0.5, 4.0: 2 and 1/4
+        p = R.problem(L, (0.4, -1.3, 0.7))
+        K = np.zeros(7)
+        lib.frame_consts(ctypes.byref(p), K.ctypes.data_as(_P))
+        pow2 = bool(K[5])
+        assert pow2 == (L in (0.5, 4.0))
+        sc = float(K[4]) if pow2 else 1.0
+        assert sc == (1.0 / L if pow2 else 1.0)
+        for at in range(0, len(radii), 16):
+            rs = radii[at:at + 16]
+            _, loop = _tables(lib, p, [(0.1 * i, -0.2 * i, r) for i, r in enumerate(rs.tolist())])
+            want = [(r * sc) * (r * sc) for r in rs.tolist()]
+            assert (_bits(loop[:len(rs), 2]) == _bits(want)).all(), (L, at)
 
 
 # ----------------------------------------------------------------------------

@@ -249,6 +249,44 @@ def test_unreached_circle_changes_nothing(engine, form):
     assert circled[2] == 0
 
 
+@pytest.mark.parametrize("counted", (True, False))
+@pytest.mark.parametrize("form", ("controls", "chained soa", "chained tiled"))
+def test_obstacle_entries_without_circles(engine, form, counted):
+    """The obstacle entries with n_obstacles = 0 (they launch the plain
+    kernels), reached through a DeviceEpisode whose hook takes them without
+    circles, with a counted and with a NULL n_blocked_out: 6 steps (max_steps
+    = 3: a restart included) over 1026 candidates (two full 512-tiles and one of
+    a single pair) leave the log, its raw bytes and the EpisodeState bytes of
+    the plain entries, and count nothing."""
+    from diplomjourney_amd.episode import DeviceEpisode
+    n_steps, n = 3, 1026
+    batches = [R.grid_batch(n, n_steps, 800 + i) for i in range(3)]
+
+    class ObstacleEntries(DeviceEpisode):
+        def _obstacle_args(self):
+            return None, 0, self.n_blocked.data_ptr() if counted else None
+
+    def run(cls):
+        ep = cls(engine, n, n_steps, integrator="rect+cum", start=R.START, target=R.TARGET,
+                 incumbent0=INC_MAX, L=0.5, chain=form.startswith("chained"), max_steps=3,
+                 log_capacity=8)
+        if counted:
+            ep.n_blocked.fill_(77)       # (the obstacle entries zero it on the stream)
+        res = [_resident(v, b, form == "chained tiled") for v, b in batches]
+        for i in range(6):
+            ep.step(controls=res[i % 3])
+        log = ep.read_log()
+        torch.cuda.synchronize()
+        assert ep.chain_error() == 0
+        assert len(log) == 6 and max(r.episode for r in log) >= 2, "no restart"
+        return ([bytes(r) for r in log], ep.log.cpu().numpy().tobytes(),
+                ep.state.cpu().numpy().tobytes(), int(ep.n_blocked.item()))
+
+    plain, entries = run(DeviceEpisode), run(ObstacleEntries)
+    assert entries[:3] == plain[:3]
+    assert plain[3] == (77 if counted else 0) and entries[3] == 0
+
+
 # ----------------------------------------------------------------------------
 # 6. everything blocked
 # ----------------------------------------------------------------------------

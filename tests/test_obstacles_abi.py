@@ -2,13 +2,13 @@
 argument checks (all before any HIP call) and the barrier list of
 math_model_tree.  No GPU."""
 import ctypes
-import math
 import os
 import re
 import subprocess
 
 import pytest
 
+import obstacle_cases
 from diplomjourney_amd import abi, native
 
 HEADER = native.HEADER
@@ -70,14 +70,11 @@ def test_argument_validation_without_gpu(L):
                                                 a["n"], a["ns"], a["integ"], a["st"], a["ws"],
                                                 a["wsb"], a["nb"], None)
 
-    many = _circles(*[(float(i), 0.0, 0.1) for i in range(abi.MPC_MAX_OBSTACLES + 1)])
+    rejected = obstacle_cases.rejected_circles()
+    assert len(rejected) == 17
     for call in (argmin, partials):
-        assert call(n_obs=-1) == abi.MPC_ERR_ARG
-        assert call(obs=many, n_obs=abi.MPC_MAX_OBSTACLES + 1) == abi.MPC_ERR_ARG
-        assert call(obs=None, n_obs=1) == abi.MPC_ERR_ARG
-        for bad in ((math.nan, 0, 1), (0, math.inf, 1), (-math.inf, 0, 1), (0, 0, math.nan),
-                    (0, 0, math.inf), (0, 0, 0.0), (0, 0, -1.0)):
-            assert call(obs=_circles((1, 1, 1), bad), n_obs=2) == abi.MPC_ERR_ARG, bad
+        for what, (obs, n_obs) in rejected.items():
+            assert call(obs=obs, n_obs=n_obs) == abi.MPC_ERR_ARG, what
         # the checks of the entries without obstacles hold as well
         assert call(p=None) == abi.MPC_ERR_ARG
         assert call(n=0) == abi.MPC_ERR_ARG

@@ -26,63 +26,54 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+from tools import cost_timing  # noqa: E402
+
 VARIANTS = (("plain_a", None), ("obstacles_0", 0), ("obstacles_1", 1), ("obstacles_4", 4),
             ("obstacles_16", 16), ("obstacles_4_counted", 4), ("plain_b", None))
 
 
 def circles(n):
     """n small circles beside the path from (0, 0) to the target (2, 3): never
-    entered (the test is straight-line code: its cost does not depend on where
-    they are)."""
-    return [(0.6 + 0.1 * i, -0.5, 0.02) for i in range(n)]
+    entered."""
+    return cost_timing.circles(n, lambda i: (0.6 + 0.1 * i, -0.5))
 
 
-def quantile(xs, q):
-    xs = sorted(xs)
-    pos = q * (len(xs) - 1)
-    lo = int(pos)
-    hi = min(lo + 1, len(xs) - 1)
-    return xs[lo] + (xs[hi] - xs[lo]) * (pos - lo)
+def episode_class():
+    """DeviceEpisode for the measured rows: the obstacle entries with no
+    circles too (obstacles_0: their dispatch of the plain kernels), and
+    n_blocked_out = NULL (no memset node on the stream: the launches alone)
+    except in the row that shows what the count costs."""
+    from diplomjourney_amd.episode import DeviceEpisode
+
+    class MeasuredEpisode(DeviceEpisode):
+        obstacle_entries = counted = False
+
+        def _obstacle_args(self):
+            if not (self._n_obs or self.obstacle_entries):
+                return None
+            return self._obs, self._n_obs, self.n_blocked.data_ptr() if self.counted else None
+
+    return MeasuredEpisode
 
 
 def measure(eng, form, n_cand, n_steps, steps, warmup, pool):
     import torch
-    from diplomjourney_amd.episode import DeviceEpisode
     chained = form == "chained_tiled"
     eps = {}
     for name, n in VARIANTS:
-        ep = DeviceEpisode(eng, n_cand, n_steps, integrator="rect+cum", chain=chained,
-                           log_capacity=64, obstacles=circles(n or 0))
-        ep._obstacle_entries = n == 0
-        # n_blocked_out = NULL (no memset node on the stream: the launches alone)
-        # except in the row that shows what the count costs
-        ep._count_blocked = name.endswith("_counted")
+        ep = episode_class()(eng, n_cand, n_steps, integrator="rect+cum", chain=chained,
+                             log_capacity=64, obstacles=circles(n or 0))
+        ep.obstacle_entries = n == 0
+        ep.counted = name.endswith("_counted")
         eps[name] = ep
-    batch = 0
-    for _ in range(warmup):
-        for name, _ in VARIANTS:
-            eps[name].step(controls=pool[batch % len(pool)])
-            batch += 1
-    torch.cuda.synchronize()
-    events = {name: [] for name, _ in VARIANTS}
-    for i in range(steps):
-        # rotate the order, so no variant always follows the same one
-        order = VARIANTS[i % len(VARIANTS):] + VARIANTS[:i % len(VARIANTS)]
-        for name, _ in order:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            eps[name].step(events=ev, controls=pool[batch % len(pool)])
-            batch += 1
-            events[name].append(ev)
+    events = cost_timing.alternate(
+        VARIANTS, warmup, steps,
+        lambda name, _n, batch, ev: eps[name].step(events=ev, controls=pool[batch % len(pool)]))
     for ep in eps.values():
         ep.flush()
     torch.cuda.synchronize()
-    errors = {name: ep.chain_error() for name, ep in eps.items()}
-    rows = {}
-    for name, evs in events.items():
-        us = [a.elapsed_time(b) * 1e3 for a, b in evs]
-        rows[name] = {"median_us": quantile(us, 0.5), "p25_us": quantile(us, 0.25),
-                      "p75_us": quantile(us, 0.75), "mean_us": sum(us) / len(us),
-                      "steps": len(us), "chain_error": errors[name]}
+    rows = {name: {**cost_timing.summary(evs, "steps"), "chain_error": eps[name].chain_error()}
+            for name, evs in events.items()}
     a, b, z = rows["plain_a"], rows["plain_b"], rows["obstacles_0"]
     base = 0.5 * (a["median_us"] + b["median_us"])
     for name, _ in VARIANTS:

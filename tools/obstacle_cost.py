@@ -21,23 +21,16 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+from tools import cost_timing  # noqa: E402
+
 VARIANTS = (("partials_a", None), ("obstacles_0", 0), ("obstacles_1", 1), ("obstacles_4", 4),
             ("obstacles_16", 16), ("partials_b", None))
 
 
 def circles(n):
-    """n small circles on a ring the candidates cross (the test is straight-line
-    code: its cost does not depend on where they are)."""
-    return [(0.3 * math.cos(0.3 + 0.15 * i), 0.3 * math.sin(0.3 + 0.15 * i), 0.02)
-            for i in range(n)]
-
-
-def quantile(xs, q):
-    xs = sorted(xs)
-    pos = q * (len(xs) - 1)
-    lo = int(pos)
-    hi = min(lo + 1, len(xs) - 1)
-    return xs[lo] + (xs[hi] - xs[lo]) * (pos - lo)
+    """n small circles on a ring the candidates cross."""
+    return cost_timing.circles(
+        n, lambda i: (0.3 * math.cos(0.3 + 0.15 * i), 0.3 * math.sin(0.3 + 0.15 * i)))
 
 
 def measure(eng, mode, n_cand, n_steps, launches, warmup, pool_batches):
@@ -56,8 +49,10 @@ def measure(eng, mode, n_cand, n_steps, launches, warmup, pool_batches):
     obs = {n: make_obstacles(circles(n)) for _, n in VARIANTS if n is not None}
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-    def launch(n, batch):
+    def launch(_name, n, batch, events):
         v, b = pool[batch % len(pool)]
+        if events:
+            events[0].record()
         if n is None:
             st = lib.mpc_rollout_partials(ctypes.byref(prob), v.data_ptr(), b.data_ptr(), n_cand,
                                           n_steps, integ, None, ws.data_ptr(), ws_bytes, stream)
@@ -66,31 +61,12 @@ def measure(eng, mode, n_cand, n_steps, launches, warmup, pool_batches):
                 ctypes.byref(prob), obs[n][0], obs[n][1], v.data_ptr(), b.data_ptr(), n_cand,
                 n_steps, integ, None, ws.data_ptr(), ws_bytes, None, stream)
         native.check(st, "rollout partials")
+        if events:
+            events[1].record()
 
-    batch = 0
-    for _ in range(warmup):
-        for _, n in VARIANTS:
-            launch(n, batch)
-            batch += 1
+    events = cost_timing.alternate(VARIANTS, warmup, launches, launch)
     torch.cuda.synchronize()
-    events = {name: [] for name, _ in VARIANTS}
-    for i in range(launches):
-        # rotate the order, so no variant always follows the same one
-        order = VARIANTS[i % len(VARIANTS):] + VARIANTS[:i % len(VARIANTS)]
-        for name, n in order:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch(n, batch)
-            e1.record()
-            batch += 1
-            events[name].append((e0, e1))
-    torch.cuda.synchronize()
-    rows = {}
-    for name, evs in events.items():
-        us = [a.elapsed_time(b) * 1e3 for a, b in evs]
-        rows[name] = {"median_us": quantile(us, 0.5), "p25_us": quantile(us, 0.25),
-                      "p75_us": quantile(us, 0.75), "mean_us": sum(us) / len(us),
-                      "launches": len(us)}
+    rows = {name: cost_timing.summary(evs, "launches") for name, evs in events.items()}
     a, b, z = rows["partials_a"], rows["partials_b"], rows["obstacles_0"]
     lo, hi = sorted((a["median_us"], b["median_us"]))
     base = 0.5 * (lo + hi)
