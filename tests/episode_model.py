@@ -216,11 +216,15 @@ class EpisodeModel(P.OracleMpcEpisode):
         return V, B, seed
 
     # -- the update -------------------------------------------------------------
-    def advance(self, results, incumbent=None, end_chain=True):
+    def advance(self, results, incumbent=None, end_chain=True, restart=True):
         """advance_from_results + episode_advance + episode_prepare over the
         gathered rows (a list of Result, or one oracle.parity ROW); returns the
         log record as a dict of mpc_episode_log_t's fields.  `incumbent`, when
-        given, must be the model's own (OracleMpcEpisode's signature)."""
+        given, must be the model's own (OracleMpcEpisode's signature).
+        restart=False is episode_advance<false> (the batched robots of
+        csrc/mpc_episodes.h): a step that ends the episode returns right after
+        its log record — no restart, no prepare, so t, K and seed stay those
+        of the step that ended it."""
         if isinstance(results, np.ndarray):
             results = [result_from_row(results)]
         assert incumbent is None or incumbent == self.incumbent
@@ -299,6 +303,8 @@ class EpisodeModel(P.OracleMpcEpisode):
         rec.update(status=status, x=self.x, y=self.y, phi=self.phi, v=self.v, beta=self.beta)
         tr.update(status=status, ended=ended)
         self.trace = tr
+        if ended and not restart:
+            return rec
         if ended:
             self.restart()
         self.prepare()

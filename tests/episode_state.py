@@ -47,6 +47,58 @@ class EpisodeState(ctypes.Structure):
                 ("pad2_", ctypes.c_uint8 * 120)]         # sizeof: a multiple of 128
 
 
+class RobotState(ctypes.Structure):
+    """One robot of the batched device episodes (csrc/mpc_episodes.h): the
+    head and the stale trajectory as in EpisodeState, then what
+    k_episodes_run carries across launches.  csrc/mpc_episodes.h parses in
+    the host-only harness build (its kernels as ordinary device functions,
+    without their launch bounds), so check_robot_layout() asserts the size
+    and every offset against the compiler's; the library's own
+    mpc_episodes_state_bytes is compared with the mirror as well
+    (tests/test_robots_model_cpu.py)."""
+    _fields_ = [("h", EpisodeHead), ("st", StaleTraj), ("stop", I32), ("calls", I32),
+                ("candidates", I64)]
+
+
+def check_robot_layout():
+    """RobotState's size and offsets, sizeof(mpc_episode_config_t) and the
+    configurations' offset for one robot: mirror == compiler."""
+    import harness
+    from diplomjourney_amd.abi import MpcEpisodeConfig
+    mine = [ctypes.sizeof(RobotState)] + [getattr(RobotState, n).offset
+                                          for n, _ in RobotState._fields_]
+    mine += [ctypes.sizeof(MpcEpisodeConfig), robots_cfg_offset(1)]
+    theirs = harness.robot_layout()
+    assert mine == theirs, f"(mirror, compiler): {mine} {theirs}"
+    assert RobotState.st.offset == ctypes.sizeof(EpisodeHead) == 8 * (
+        STORED_WORDS - ctypes.sizeof(StaleTraj) // 8)
+    return len(mine)
+
+
+def robots_cfg_offset(n):
+    """episodes_cfg_offset: where the n robots' configurations start."""
+    return (n * ctypes.sizeof(RobotState) + 255) & ~255
+
+
+def robots_state_bytes(n):
+    """mpc_episodes_state_bytes(n) from the mirrors."""
+    from diplomjourney_amd.abi import MpcEpisodeConfig
+    return robots_cfg_offset(n) + n * ctypes.sizeof(MpcEpisodeConfig)
+
+
+def read_robots(raw, n):
+    """(RobotState[n], the n configurations' bytes) of a batch's state
+    (bytes, or a uint8 tensor, device or host)."""
+    from diplomjourney_amd.abi import MpcEpisodeConfig
+    if not isinstance(raw, (bytes, bytearray)):
+        raw = raw.detach().cpu().numpy().tobytes()
+    assert len(raw) == robots_state_bytes(n)
+    size = ctypes.sizeof(RobotState)
+    robots = [RobotState.from_buffer_copy(raw[r * size:(r + 1) * size]) for r in range(n)]
+    return robots, raw[robots_cfg_offset(n):robots_cfg_offset(n)
+                       + n * ctypes.sizeof(MpcEpisodeConfig)]
+
+
 _STRUCTS = (("Consts", Consts), ("EpisodeHead", EpisodeHead), ("StaleTraj", StaleTraj),
             ("EarlyPub", EarlyPub), ("EpisodeState", EpisodeState))
 _SIZE_ORDER = ("EpisodeHead", "StaleTraj", "EarlyPub", "EpisodeState", "Consts")
@@ -130,6 +182,30 @@ def leaves(obj, prefix="", raw=None, base=0):
 def _flat_len(arr):
     n = len(arr)
     return n * _flat_len(arr[0]) if isinstance(arr[0], ctypes.Array) else n
+
+
+def leaf_values(obj, prefix=""):
+    """[(name, value)] of every scalar of a mirror, in leaves()' order, for a
+    report: an element of an array is named by its own indices (st.ot[1][2];
+    leaves() counts a 2-D array's elements flat) and a double is given as hex."""
+    def walk(val, name):
+        if isinstance(val, ctypes.Structure):
+            return leaf_values(val, name + ".")
+        if isinstance(val, ctypes.Array):
+            return [q for i in range(len(val)) for q in walk(val[i], f"{name}[{i}]")]
+        return [(name, val.hex() if isinstance(val, float) else val)]
+    return [q for n, _ in obj._fields_ for q in walk(getattr(obj, n), prefix + n)]
+
+
+def named_diff(got, want):
+    """[(name, got's value, want's value)] of the scalars whose bits differ
+    (diff()'s rule: padding excepted), each named by leaf_values()."""
+    def bits(val, raw):    # (two NaNs print alike: their bits then)
+        return f"{val} 0x{int.from_bytes(raw, 'little'):x}"
+    rows = zip(leaves(got), leaves(want), leaf_values(got), leaf_values(want))
+    return [(name, a, b) if a != b else (name, bits(a, ra), bits(b, rb))
+            for (flat, ra), (_, rb), (name, a), (_, b) in rows
+            if ra != rb and not flat.startswith(("pad0_", "pad1_", "pad2_"))]
 
 
 def diff(got, want, skip=()):

@@ -1,4 +1,5 @@
 """Builds and loads the host test harnesses (trig_harness.cpp, replica_harness.cpp)."""
+import contextlib
 import ctypes
 import glob
 import os
@@ -82,6 +83,16 @@ def episode_layout(n):
     return [int(q) for q in out[:n]], int(out[n])
 
 
+def robot_layout():
+    """replica_robot_layout's eight values."""
+    out = np.full(8, -1, dtype=np.int64)
+    L = replica_lib()
+    L.replica_robot_layout.argtypes = [_P]
+    L.replica_robot_layout.restype = None
+    L.replica_robot_layout(out.ctypes.data_as(_P))
+    return [int(q) for q in out]
+
+
 def replica_consts(problem, nbytes):
     """consts_from_problem(problem) as the library's host build forms it: raw bytes."""
     buf = ctypes.create_string_buffer(nbytes)
@@ -150,6 +161,26 @@ def _install_device_estimates(L, beta):
     q = np.unique(q)
     r = device_rcp(q)
     L.replica_set_rcp_table(q.ctypes.data_as(_P), r.ctypes.data_as(_P), len(q))
+
+
+@contextlib.contextmanager
+def estimates_installed(beta, device=True):
+    """One table of the device's reciprocal estimates (one fetch, of every
+    tan_small denominator of `beta`) kept installed across any number of
+    replica_rollout calls (device_estimates=False in them: that flag fetches
+    and removes a table per call).  Yields replica_rcp_misses, to be asserted 0
+    before the block ends.  device=False (a CPU run): nothing is fetched, the
+    host's 1.0 / q serves, and the count is 0."""
+    L = replica_lib()
+    beta = np.ascontiguousarray(beta, dtype=np.float64)
+    on = bool(device) and beta[np.isfinite(beta)].size > 0
+    if on:
+        _install_device_estimates(L, beta)
+    try:
+        yield (lambda: int(L.replica_rcp_misses())) if on else (lambda: 0)
+    finally:
+        if on:
+            L.replica_set_rcp_table(None, None, 0)
 
 
 def replica_fulltree(problem, V, B, integ="rect", device_estimates=False, device_consts=False,

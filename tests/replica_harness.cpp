@@ -216,7 +216,37 @@ extern "C" int replica_fulltree(const mpc_fulltree_problem_t* p, const double* V
 #undef __global__
 #define __global__ __device__
 #include "../diplomjourney_amd/csrc/mpc_episode.h"
+// (mpc_episodes.h: the batched robots' RobotState, for its layout alone; its
+// two kernels and those of the headers it includes are parsed the same way,
+// without their launch bounds, which only a kernel may carry.  The price:
+// mpc_episodes.h and everything it includes (mpc_argmin.h, mpc_generated.h,
+// mpc_lanes.h, mpc_sampler.h, mpc_winner.h) are now part of EVERY build of
+// this harness, so a construct in one of them that the host pass cannot
+// parse breaks all replica tests, not only the RobotState layout check.  If
+// that happens, move this include and replica_robot_layout into a harness of
+// their own rather than weaken the header.)
+#pragma push_macro("__launch_bounds__")
+#undef __launch_bounds__
+#define __launch_bounds__(...)
+#include "../diplomjourney_amd/csrc/mpc_episodes.h"
+#pragma pop_macro("__launch_bounds__")
 #pragma pop_macro("__global__")
+
+// out[0..8): sizeof(RobotState), offsetof of h, st, stop, calls, candidates,
+// sizeof(mpc_episode_config_t), episodes_cfg_offset(1) (check_robot_layout of
+// tests/episode_state.py states the same order).  Kept apart from
+// replica_episode_layout, whose value count tests/test_episode_model_cpu.py pins.
+extern "C" void replica_robot_layout(int64_t* out) {
+  using namespace mpc;
+  out[0] = sizeof(RobotState);
+  out[1] = offsetof(RobotState, h);
+  out[2] = offsetof(RobotState, st);
+  out[3] = offsetof(RobotState, stop);
+  out[4] = offsetof(RobotState, calls);
+  out[5] = offsetof(RobotState, candidates);
+  out[6] = sizeof(mpc_episode_config_t);
+  out[7] = static_cast<int64_t>(episodes_cfg_offset(1));
+}
 
 // out[0..n): sizeof of EpisodeHead, StaleTraj, EarlyPub, EpisodeState, Consts;
 // offsetof of every field of Consts, EpisodeHead, StaleTraj, EarlyPub,
