@@ -226,6 +226,7 @@ __device__ inline void episode_early_prepare(const mpc_episode_config_t& c, cons
   E.alt = early_pose_ok(c, S, E.x, E.y) ? 1 : 0;
 }
 
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ void k_episode_reset(mpc_episode_config_t c, EpisodeState* __restrict__ S) {
   if (threadIdx.x != 0) return;
   EpisodeHead H = {};
@@ -241,6 +242,7 @@ __global__ void k_episode_reset(mpc_episode_config_t c, EpisodeState* __restrict
   for (int q = 0; q < kPubWords; ++q) S->chain_pub[q] = 0ull;
   S->gathered_tag = 0ull;
 }
+#endif
 
 // _turn_target (math_model_tree.py:142-215 sectors; sign = +1 left, -1 right).
 __device__ inline void turn_target(double ax, double ay, double aphi, double d, double R,

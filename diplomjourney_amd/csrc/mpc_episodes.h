@@ -57,6 +57,7 @@ __host__ __device__ inline size_t episodes_cfg_offset(int n) {
   return (static_cast<size_t>(n) * sizeof(RobotState) + 255) & ~static_cast<size_t>(255);
 }
 
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ void k_episodes_reset(const mpc_episode_config_t* __restrict__ cfgs, int n,
                                  RobotState* __restrict__ robots) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -71,6 +72,7 @@ __global__ void k_episodes_reset(const mpc_episode_config_t* __restrict__ cfgs, 
   R.stop = (ex * ex + ey * ey <= c.eps) ? MPC_EP_ARRIVED : 0;
   robots[r] = R;
 }
+#endif
 
 // Two candidates with constant controls (v[j], b[j]) over n_steps, their
 // recurrences in one loop — independent chains the scheduler interleaves —

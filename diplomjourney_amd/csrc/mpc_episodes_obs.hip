@@ -1,0 +1,28 @@
+// mpc_episodes_obs.hip — the second translation unit of libmpc_rollout.so: the
+// batched robots' episode kernel with keep-out circles (mpc_episodes_obs.h)
+// and its launch.  The entry, its checks and the plain kernel stay in
+// mpc_rollout.hip (episodes_run); why the kernels are compiled apart:
+// mpc_episodes_obs_launch.h.
+// (the headers' plain, non-template kernels are mpc_rollout.hip's: one definition
+// per library)
+#define MPC_TEMPLATES_ONLY
+#include "mpc_episodes_obs_launch.h"
+
+#include "mpc_dispatch.h"
+#include "mpc_episodes_obs.h"
+
+namespace mpc {
+
+void launch_episodes_run_obs(hipStream_t st, int32_t integrator, const Obstacles& world, int n_obs,
+                             int n_robots, const mpc_episode_config_t* cfgs, RobotState* robots,
+                             int n_steps, int max_calls, mpc_episode_log_t* log, int cap,
+                             mpc_episodes_progress_t* progress, int64_t* n_blocked) {
+  dispatch_mode(integrator, [&](auto I, auto R) {
+    dispatch_nobs<true>(n_obs, [&](auto NOBS) {
+      k_episodes_run_obs<I, R, NOBS><<<n_robots, kBlock, 0, st>>>(
+          world, cfgs, robots, n_steps, max_calls, log, cap, progress, n_blocked);
+    });
+  });
+}
+
+}  // namespace mpc

@@ -300,10 +300,12 @@ __device__ void collect_local_candidate(const Rec* __restrict__ part, int n_part
 // The overlapped exchange's hand-off: after the all_gather of step `tag`'s
 // candidates (same stream, so the collective's stores are complete), publish
 // the tag.  One coherent 8-B store (relaxed, agent scope: `sc1`).
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ void k_exchange_mark(EpisodeState* __restrict__ S, uint32_t tag) {
   if (threadIdx.x == 0) __hip_atomic_store(&S->gathered_tag, static_cast<uint64_t>(tag),
                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+#endif
 
 constexpr int kXchgLdsRanks = 32;   // gathered candidates staged in the ring's LDS
 static_assert(kXchgLdsRanks * sizeof(mpc_candidate_t) + sizeof(EmitLds) <= sizeof(g_ring),
@@ -348,6 +350,7 @@ __device__ const mpc_candidate_t* wait_gathered(EpisodeState* S, uint32_t tag,
   return dst;
 }
 
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ __launch_bounds__(64) void k_episode_advance(mpc_episode_config_t c,
                                                         EpisodeState* __restrict__ S,
                                                         const mpc_result_t* __restrict__ res,
@@ -355,6 +358,7 @@ __global__ __launch_bounds__(64) void k_episode_advance(mpc_episode_config_t c,
                                                         int cap) {
   advance_from_results(c, S, res, n, log, cap);
 }
+#endif
 
 // Block 0, all threads, after the episode head is stored: publish its Consts
 // and t as tagged words (relaxed agent-scope atomic stores: coherent, and each
@@ -624,6 +628,7 @@ __device__ void p2p_complete(const mpc_episode_config_t& c, EpisodeState* S, voi
 // The mailboxes' self-test (mpc_mailbox_ping): lane r stores `tag` into
 // rank r's ping word for this rank, then every lane waits (~0.1 s at most)
 // for its rank's word in this mailbox; ok[0] = 1 if all `world` arrived.
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ __launch_bounds__(64) void k_mailbox_ping(void* mb, uint32_t tag, int32_t* ok) {
   MailHdr* hdr = static_cast<MailHdr*>(mb);
   const int world = hdr->world, rank = hdr->rank;
@@ -642,6 +647,7 @@ __global__ __launch_bounds__(64) void k_mailbox_ping(void* mb, uint32_t tag, int
   const bool all = __ballot(!seen) == 0;
   if (r == 0) ok[0] = all ? 1 : 0;
 }
+#endif
 
 template <int INTEG, int ROT, bool TILED>
 __global__ __launch_bounds__(kBlock) void k_episode_p2p_flush(

@@ -63,6 +63,7 @@ __device__ inline void episode_grids(const mpc_episode_config_t& c, const Episod
   nb_out = nb < kEpMaxGrid ? nb : kEpMaxGrid;
 }
 
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ __launch_bounds__(kBlock) void k_episode_sample(
     mpc_episode_config_t c, EpisodeState* __restrict__ S, int64_t n_cand, int n_steps,
     int64_t base, double* __restrict__ v, double* __restrict__ b, int pairs) {
@@ -112,6 +113,7 @@ __global__ __launch_bounds__(kBlock) void k_episode_sample(
   sample_items(s_grid, n_grid, n_cand, n_steps, seed, base, c.enumerate ? 2 : 1, v, b, n_cand,
                pairs);
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // Generated controls (inputs "generated", mpc_episode_generate_step): the

@@ -286,6 +286,7 @@ __device__ int select_index(const mpc_result_t* __restrict__ res, int n, uint64_
   return best;
 }
 
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ void k_select_winner(const mpc_result_t* __restrict__ res, int n, double incumbent,
                                 mpc_result_t* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -294,5 +295,6 @@ __global__ void k_select_winner(const mpc_result_t* __restrict__ res, int n, dou
   *out = res[best];
   out->found = (bk != ~0ull && out->cost < incumbent) ? 1 : 0;
 }
+#endif
 
 }  // namespace mpc

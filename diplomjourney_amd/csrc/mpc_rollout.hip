@@ -24,9 +24,11 @@
 #include "mpc_chain.h"
 #include "mpc_comm.h"
 #include "mpc_device.h"
+#include "mpc_dispatch.h"
 #include "mpc_episode.h"
 #include "mpc_episode_obs.h"
 #include "mpc_episodes.h"
+#include "mpc_episodes_obs_launch.h"
 #include "mpc_exchange.h"
 #include "mpc_finalize.h"
 #include "mpc_ftepisodes.h"
@@ -67,11 +69,6 @@ int64_t rollout_grid(int64_t n_cand) {
   return std::max<int64_t>(1, std::min<int64_t>(cdiv(n_cand, kBlock * CPL), kMaxBlocks));
 }
 
-template <int V>
-using IC = std::integral_constant<int, V>;
-template <bool V>
-using BC = std::integral_constant<bool, V>;
-
 // integrator = MPC_INTEG_* [| MPC_HEADING_ROTATE | MPC_HEADING_CUMULATIVE]
 //   -> f(IC<INTEG>, IC<ROT>), ROT 0 direct heading, 1 rotation, 2 (kRotCum)
 //   rotation from the identity with the pose applied last (rect only).
@@ -88,7 +85,6 @@ int mode_ok(int32_t integrator, bool allow_cum = true, bool allow_tiled = false)
   return MPC_OK;
 }
 
-inline bool is_cum(int32_t integrator) { return (integrator & MPC_HEADING_CUMULATIVE) != 0; }
 inline bool is_tiled(int32_t integrator) { return (integrator & MPC_LAYOUT_TILED) != 0; }
 
 // MPC_LAYOUT_TILED controls: v = the buffer's base (16-B aligned), beta =
@@ -167,38 +163,6 @@ int64_t resident_blocks() {
   return cache[dev];
 }
 
-// Runtime bools -> f(BC<b0>{}, BC<b1>{}, ...): one call per combination, so a
-// kernel's bool template parameters can follow runtime decisions.
-template <class F, class... Bs>
-void dispatch_bools(F&& f, bool b, Bs... rest) {
-  if constexpr (sizeof...(rest) == 0) {
-    b ? f(BC<true>{}) : f(BC<false>{});
-  } else {
-    b ? dispatch_bools([&](auto... t) { f(BC<true>{}, t...); }, rest...)
-      : dispatch_bools([&](auto... t) { f(BC<false>{}, t...); }, rest...);
-  }
-}
-
-// integrator -> f(IC<INTEG>, BC<ROT>): the integrator and whether the heading is
-// a rotation.  As it stands, the full-tree kernels' dispatch (direct or rotation
-// heading only: their entries refuse MPC_HEADING_CUMULATIVE).  The tags convert
-// to their values, so a lambda's (auto I, auto R) go straight into k<I, R>.
-template <class F>
-void dispatch_integ_rot(int32_t integrator, F&& f) {
-  dispatch_bools(
-      [&](auto rect, auto rot) { f(IC<rect ? MPC_INTEG_RECT : MPC_INTEG_QK21>{}, rot); },
-      (integrator & 0xff) == MPC_INTEG_RECT, (integrator & MPC_HEADING_ROTATE) != 0);
-}
-
-// integrator -> f(IC<INTEG>, IC<ROT>), ROT as described above mode_ok.
-template <class F>
-void dispatch_mode(int32_t integrator, F&& f) {
-  if ((integrator & 0xff) == MPC_INTEG_RECT && is_cum(integrator))
-    f(IC<MPC_INTEG_RECT>{}, IC<kRotCum>{});
-  else
-    dispatch_integ_rot(integrator, [&](auto integ, auto rot) { f(integ, IC<rot ? 1 : 0>{}); });
-}
-
 // The fused episode launch is sized to ONE resident round of its instantiation:
 // each block's end-of-launch hand-off (sc1 store + counter atomic) is then paid
 // once per block, not once per tile round.
@@ -257,18 +221,6 @@ int check_obstacles(const mpc_obstacle_t* obs, int32_t n) {
 ObstacleArgs host_obstacles(const Consts& K, const mpc_obstacle_t* obs, int n, bool cum) {
   const Obstacles W = world_obstacles(obs, n);
   return ObstacleArgs{cum ? frame_obstacles(K, W, n) : W, W};
-}
-
-// n_obs -> f(IC<NOBS>) over the instantiations: 4 or all, and with ONE also 1.
-template <bool ONE, class F>
-void dispatch_nobs(int n_obs, F&& f) {
-  if constexpr (ONE) {
-    if (n_obs <= 1) return f(IC<1>{});
-  }
-  if (n_obs <= 4)
-    f(IC<4>{});
-  else
-    f(IC<MPC_MAX_OBSTACLES>{});
 }
 
 // The obstacle variant of launch_rollout / the states launch: the same grid
@@ -498,6 +450,42 @@ int episode_chain_step(const mpc_episode_config_t* cfg, void* state,
           });
       },
       length_pow2(cfg->L), is_tiled(integrator));
+  return last_hip_status();
+}
+
+// mpc_episodes_run (no circles, no count) and mpc_episodes_run_obstacles, in
+// the same way: the circles are checked first; with none the plain kernel runs
+// and a count, if asked for, is zeroed on the stream; max_calls == 0 launches
+// nothing and writes nothing.
+int episodes_run(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                 int32_t n_robots, int32_t n_steps, int32_t integrator, int32_t max_calls,
+                 mpc_episode_log_t* log, int32_t log_capacity, mpc_episodes_progress_t* progress,
+                 int64_t* n_blocked_out, mpc_stream_t stream) {
+  if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
+  if (!state || n_robots < 1 || n_robots > 65535 || n_steps < 1 || n_steps > MPC_MAX_STEPS ||
+      max_calls < 0 || log_capacity < 0 || (log && log_capacity < 1))
+    return MPC_ERR_ARG;
+  if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
+  if (max_calls == 0) return MPC_OK;
+  char* s = static_cast<char*>(state);
+  const mpc_episode_config_t* dcfg =
+      reinterpret_cast<const mpc_episode_config_t*>(s + episodes_cfg_offset(n_robots));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  RobotState* robots = reinterpret_cast<RobotState*>(s);
+  const int cap = log ? log_capacity : 0;
+  if (n_obstacles == 0 && n_blocked_out &&
+      hipMemsetAsync(n_blocked_out, 0, static_cast<size_t>(n_robots) * sizeof(*n_blocked_out),
+                     st) != hipSuccess)
+    return MPC_ERR_HIP;
+  if (n_obstacles == 0)
+    dispatch_mode(integrator, [&](auto I, auto R) {
+      k_episodes_run<I, R><<<n_robots, kBlock, 0, st>>>(dcfg, robots, n_steps, max_calls, log, cap,
+                                                        progress);
+    });
+  else
+    launch_episodes_run_obs(st, integrator, world_obstacles(obstacles, n_obstacles), n_obstacles,
+                            n_robots, dcfg, robots, n_steps, max_calls, log, cap, progress,
+                            n_blocked_out);
   return last_hip_status();
 }
 
@@ -1450,22 +1438,17 @@ int mpc_episodes_reset(const mpc_episode_config_t* cfgs, int32_t n_robots, void*
 int mpc_episodes_run(void* state, int32_t n_robots, int32_t n_steps, int32_t integrator,
                      int32_t max_calls, mpc_episode_log_t* log, int32_t log_capacity,
                      mpc_episodes_progress_t* progress, mpc_stream_t stream) {
-  if (!state || n_robots < 1 || n_robots > 65535 || n_steps < 1 || n_steps > MPC_MAX_STEPS ||
-      max_calls < 0 || log_capacity < 0 || (log && log_capacity < 1))
-    return MPC_ERR_ARG;
-  if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
-  if (max_calls == 0) return MPC_OK;
-  char* s = static_cast<char*>(state);
-  const mpc_episode_config_t* dcfg =
-      reinterpret_cast<const mpc_episode_config_t*>(s + episodes_cfg_offset(n_robots));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  RobotState* robots = reinterpret_cast<RobotState*>(s);
-  const int cap = log ? log_capacity : 0;
-  dispatch_mode(integrator, [&](auto I, auto R) {
-    k_episodes_run<I, R><<<n_robots, kBlock, 0, st>>>(dcfg, robots, n_steps, max_calls, log, cap,
-                                                      progress);
-  });
-  return last_hip_status();
+  return episodes_run(state, nullptr, 0, n_robots, n_steps, integrator, max_calls, log,
+                      log_capacity, progress, nullptr, stream);
+}
+
+int mpc_episodes_run_obstacles(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                               int32_t n_robots, int32_t n_steps, int32_t integrator,
+                               int32_t max_calls, mpc_episode_log_t* log, int32_t log_capacity,
+                               mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
+                               mpc_stream_t stream) {
+  return episodes_run(state, obstacles, n_obstacles, n_robots, n_steps, integrator, max_calls, log,
+                      log_capacity, progress, n_blocked_out, stream);
 }
 
 // ----------------------------- full tree -----------------------------------

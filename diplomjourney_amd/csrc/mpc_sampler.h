@@ -71,6 +71,7 @@ __device__ void sample_items(const double2* s_grid, uint32_t n_grid, int64_t n_c
   }
 }
 
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ __launch_bounds__(kBlock) void k_sample_controls(
     const double* __restrict__ vg, int nv, const double* __restrict__ bg, int nb, int64_t n_cand,
     int n_steps, uint64_t seed, int64_t base, int cprefix, double* __restrict__ v,
@@ -98,5 +99,6 @@ __global__ __launch_bounds__(kBlock) void k_sample_controls(
   __syncthreads();
   sample_items(s_grid, n_grid, n_cand, n_steps, seed, base, cprefix, v, b, ld, pairs, tiled);
 }
+#endif
 
 }  // namespace mpc

@@ -7,8 +7,8 @@ import numpy as np
 import torch
 
 from . import native
-from .abi import (INTEGRATORS, LOG_BYTES, PROGRESS_BYTES, MpcEpisodeConfig,
-                  MpcFulltreeEpisodeConfig)
+from .abi import (INTEGRATORS, LOG_BYTES, MPC_MAX_OBSTACLES, PROGRESS_BYTES, MpcEpisodeConfig,
+                  MpcFulltreeEpisodeConfig, make_obstacles)
 
 # numpy view of mpc_episode_log_t (include/mpc_rollout.h), 80 bytes
 _LOG_DTYPE = [("step", "<i8"), ("index", "<i8"), ("p", "<i4"), ("episode", "<i4"),
@@ -65,15 +65,30 @@ class DeviceEpisodes(_RobotBatch):
     for up to k MPC steps of every robot, with no host round trip and no
     lockstep.  cfgs: one MpcEpisodeConfig per robot (start, target and rules:
     `tree_episode_config` for run_math_model.py's loop, the reference_episode_
-    config of math_mpc for the operator scenario)."""
+    config of math_mpc for the operator scenario).
 
-    def __init__(self, engine, cfgs, n_steps=3, integrator="qk21", log_capacity=1024):
+    obstacles / set_obstacles(): keep-out circles (x, y, r) in world
+    coordinates, at most 16, ONE table for all robots (one map), with the
+    semantics of the one-shot entries (mpc_rollout_partials_obstacles): a
+    candidate that ends a step of its horizon strictly inside one never wins;
+    if all of a step's candidates do, the step has no winner (MPC_EP_STALE).
+    They are passed with every run() (mpc_episodes_run_obstacles) and are not
+    part of the state.  read_blocked(): per robot the candidates blocked in
+    the steps of the last run().  With no circles run() is the call made
+    without the feature.  Not provided: a table per robot, robots as each
+    other's obstacles."""
+
+    def __init__(self, engine, cfgs, n_steps=3, integrator="qk21", log_capacity=1024,
+                 obstacles=()):
         self.eng = engine
         self.cfgs = list(cfgs)
         self.n_steps = int(n_steps)
         self.integrator = integrator
         super().__init__(engine.device, len(self.cfgs), native.lib().mpc_episodes_state_bytes,
                          integrator, log_capacity)
+        self.n_blocked = torch.zeros(self.R, dtype=torch.int64, device=engine.device)
+        self._obs, self._n_obs, self._counted = None, 0, False
+        self.set_obstacles(obstacles)
         self.reset()
 
     def reset(self):
@@ -81,13 +96,42 @@ class DeviceEpisodes(_RobotBatch):
         self._C.mpc_episodes_reset(ctypes.byref(arr), self.R, self.state.data_ptr(),
                                    native.current_stream())
         self.progress.zero_()
+        self._counted = False        # (read_blocked(): zeros until the next run())
+
+    def set_obstacles(self, circles):
+        """The keep-out circles of the run() calls from now on."""
+        obs, n = make_obstacles(circles)
+        if n > MPC_MAX_OBSTACLES:
+            raise ValueError(f"at most {MPC_MAX_OBSTACLES} obstacles")
+        self._obs, self._n_obs = obs, n
+
+    def _obstacle_args(self):
+        """None (the plain entry), or what mpc_episodes_run_obstacles takes
+        besides: (circles, count, n_blocked_out)."""
+        if not self._n_obs:
+            return None
+        return self._obs, self._n_obs, self.n_blocked.data_ptr()
 
     def run(self, max_calls):
         """Enqueue up to max_calls MPC steps of every still-running robot."""
-        self._C.mpc_episodes_run(
-            self.state.data_ptr(), self.R, self.n_steps, self._integ, int(max_calls),
-            self.log.data_ptr(), self.log_capacity, self.progress.data_ptr(),
-            native.current_stream())
+        args = (self.R, self.n_steps, self._integ, int(max_calls), self.log.data_ptr(),
+                self.log_capacity, self.progress.data_ptr())
+        extra = self._obstacle_args()
+        self._counted = extra is not None
+        if extra is None:
+            self._C.mpc_episodes_run(self.state.data_ptr(), *args, native.current_stream())
+        else:
+            *circles, blocked = extra
+            self._C.mpc_episodes_run_obstacles(self.state.data_ptr(), *circles, *args, blocked,
+                                               native.current_stream())
+
+    def read_blocked(self):
+        """Per robot (numpy int64; syncs) the candidates that the circles
+        blocked in the steps of the last run() (zeros after a run() without
+        circles: nothing can be blocked)."""
+        if not self._counted:
+            return np.zeros(self.R, dtype=np.int64)
+        return self.n_blocked.cpu().numpy().copy()
 
 
 class DeviceFtEpisodes(_RobotBatch):

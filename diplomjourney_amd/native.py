@@ -27,6 +27,9 @@ REPO_DIR = os.path.dirname(PKG_DIR)
 LIB_NAME = "libmpc_rollout.so"
 LIB_PATH = os.path.join(PKG_DIR, LIB_NAME)
 SRC = os.path.join(PKG_DIR, "csrc", "mpc_rollout.hip")
+# every translation unit of the library, SRC first (csrc/mpc_episodes_obs_launch.h
+# says why the second one is apart)
+SOURCES = (SRC, os.path.join(PKG_DIR, "csrc", "mpc_episodes_obs.hip"))
 HEADER = os.path.join(REPO_DIR, "include", "mpc_rollout.h")
 
 _P = ctypes.c_void_p           # any device / host pointer, mpc_stream_t, mpc_comm_t
@@ -134,6 +137,8 @@ PROTOTYPES = {
     "mpc_episodes_state_bytes": (c_size_t, [_I32]),
     "mpc_episodes_reset": (c_int, [_P, _I32, _P, _P]),
     "mpc_episodes_run": (c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
+    "mpc_episodes_run_obstacles": (c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P,
+                                           _P]),
     "mpc_fulltree_episodes_state_bytes": (c_size_t, [_I32]),
     "mpc_fulltree_episodes_reset": (c_int, [_P, _I32, _P, _P]),
     "mpc_fulltree_episodes_run": (c_int, [_P, _I32, _P, _I32, _P, _I32, _D, _D, _D, _I32, _I32,
@@ -157,7 +162,7 @@ HIPCC_FLAGS = [
 
 def build(verbose=False):
     """Compile csrc/*.hip for gfx950 into the in-tree shared library."""
-    cmd = [HIPCC, *HIPCC_FLAGS, "-I", os.path.join(REPO_DIR, "include"), "-o", LIB_PATH, SRC]
+    cmd = [HIPCC, *HIPCC_FLAGS, "-I", os.path.join(REPO_DIR, "include"), "-o", LIB_PATH, *SOURCES]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)

@@ -409,7 +409,7 @@ def run_tree_episode(start, max_calls=None):
 
 
 def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, stats=None,
-                     chunk=1024):
+                     chunk=1024, obstacles=None):
     """The tree-expansion episode loop for len(starts) episodes at once, one
     robot per episode, device-resident (device_episodes.DeviceEpisodes,
     mpc_episodes_run): each robot is one block that runs its episode's MPC
@@ -419,20 +419,33 @@ def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, sta
     per launch, the log read back once per launch.  Returns [(records, stop)]
     per episode, as run_tree_episode returns them (the script's TypeError if
     an episode's first call finds no winner).  stats (optional dict) receives
-    the lockstep-equivalent steps (the longest episode's calls) and the
-    candidates rolled out (each call's |V| x |B|)."""
+    the lockstep-equivalent steps (the longest episode's calls), the
+    candidates rolled out (each call's |V| x |B|) and, as "blocked", those of
+    them that a keep-out circle blocked.
+    obstacles: keep-out circles (x, y, r), one table for all robots (one map;
+    at most 16).  None takes a copy of math_model_tree.barriers at the call,
+    the list run_tree_episode's predictive_control scores against, so that
+    the batched and the sequential driver agree; a sequence, () included,
+    overrides it.  Not provided: a table per robot, robots as each other's
+    obstacles."""
     eng = engine or _device()[0]
+    if obstacles is None:
+        from . import math_model_tree as mmt
+        obstacles = list(mmt.barriers)
     R = len(starts)
     if max_calls == 0:
         return [([], "on_target" if is_on_target(s[0], s[1], s[3], s[4]) else "max_calls")
                 for s in starts]
     cap = min(chunk, max_calls) if max_calls else chunk
     eps = DeviceEpisodes(eng, [tree_episode_config(s, max_calls) for s in starts], 3, integrator,
-                         log_capacity=cap)
+                         log_capacity=cap, obstacles=obstacles)
     records = [[] for _ in range(R)]
     found_any = np.zeros(R, dtype=bool)
+    blocked = 0
     while True:
         eps.run(cap)
+        if len(obstacles):
+            blocked += int(eps.read_blocked().sum())
         logs = eps.read_logs(first_step=[len(r) for r in records])
         calls, stop, cands = eps.read_progress()
         for r, lg in enumerate(logs):
@@ -449,6 +462,7 @@ def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, sta
     if stats is not None:
         stats["steps"] = stats.get("steps", 0) + int(calls.max(initial=0))
         stats["candidates"] = stats.get("candidates", 0) + int(cands.sum())
+        stats["blocked"] = stats.get("blocked", 0) + blocked
     return [(records[r], _stop_name(stop[r])) for r in range(R)]
 
 

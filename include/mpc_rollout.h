@@ -185,8 +185,9 @@ int mpc_rollout_finalize(const mpc_problem_t* p, const double* v_sc, const doubl
  * outside [0, MPC_MAX_OBSTACLES], obstacles NULL with n_obstacles > 0, a
  * non-finite centre, r not finite or r <= 0.  The device-resident episode
  * takes circles through mpc_episode_partials_obstacles, _step_obstacles and
- * _chain_step_obstacles (below, where what still takes none is listed); the
- * batched entry and the full tree take no obstacles.
+ * _chain_step_obstacles, the batched robots' episodes through
+ * mpc_episodes_run_obstacles (both below, where what still takes none is
+ * listed); the batched one-shot entry and the full tree take no obstacles.
  */
 #define MPC_MAX_OBSTACLES 16
 typedef struct mpc_obstacle {
@@ -432,7 +433,9 @@ int mpc_episode_chain_step(const mpc_episode_config_t* cfg, void* state, int32_t
  * so finalize, the update and the multi-GPU expand / advance step follow as
  * they are.  Without obstacles: the fused step (mpc_episode_rollout), the
  * generated step, the persistent run, the exchange and P2P chained steps,
- * mpc_episodes_run, the batched entry and the full tree. */
+ * the batched one-shot entry (mpc_rollout_argmin_batched) and the full tree
+ * with its episodes.  (The batched robots' episodes take circles through
+ * mpc_episodes_run_obstacles.) */
 int mpc_episode_partials_obstacles(void* state, const mpc_obstacle_t* obstacles,
                                    int32_t n_obstacles, const double* v_sc,
                                    const double* beta_sc, int64_t n_cand, int32_t n_steps,
@@ -672,6 +675,30 @@ int mpc_episode_chain_error(const void* state, int32_t* error, mpc_stream_t stre
  *   mpc_episodes_run     log: [R][log_capacity] rings of mpc_episode_log_t
  *                        (slot = step % capacity, nullable); progress: device
  *                        array [R], written at the end of the launch
+ *   mpc_episodes_run_obstacles   the same with keep-out circles, ONE table for
+ *                        all robots of the launch (one map), passed per call
+ *                        and not stored in the state; the semantics of
+ *                        mpc_rollout_partials_obstacles: world frame, at most
+ *                        MPC_MAX_OBSTACLES, strictly inside, step-end states
+ *                        1..N only (the start pose is not tested), a NaN state
+ *                        is inside nothing, a blocked candidate never wins; a
+ *                        step whose candidates are all blocked is the step
+ *                        without a finite cost (index -1, found 0,
+ *                        MPC_EP_STALE).  rect+cum forms the table in the frame
+ *                        of each robot's step on the device, once per step.
+ *                        The circles are checked first (MPC_ERR_ARG before any
+ *                        HIP call, as mpc_rollout_partials_obstacles); with
+ *                        valid circles every other rejection is
+ *                        mpc_episodes_run's, in its order.  n_obstacles == 0
+ *                        launches mpc_episodes_run's kernels: the same state,
+ *                        log and progress bytes.
+ *                        n_blocked_out (optional): device int64[R], WRITTEN
+ *                        (not accumulated) by every call with max_calls > 0:
+ *                        robot r's candidates blocked in the steps this call
+ *                        ran for it, 0 if it ran none (with n_obstacles == 0
+ *                        zeroed on `stream`); max_calls == 0 launches nothing
+ *                        and leaves it alone, like progress.
+ * Not provided: per-robot tables, robots as each other's obstacles.
  * ------------------------------------------------------------------------- */
 typedef struct mpc_episodes_progress {
   int32_t calls;         /* MPC steps run so far                                     */
@@ -685,6 +712,11 @@ int mpc_episodes_reset(const mpc_episode_config_t* cfgs, int32_t n_robots, void*
 int mpc_episodes_run(void* state, int32_t n_robots, int32_t n_steps, int32_t integrator,
                      int32_t max_calls, mpc_episode_log_t* log, int32_t log_capacity,
                      mpc_episodes_progress_t* progress, mpc_stream_t stream);
+int mpc_episodes_run_obstacles(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                               int32_t n_robots, int32_t n_steps, int32_t integrator,
+                               int32_t max_calls, mpc_episode_log_t* log, int32_t log_capacity,
+                               mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
+                               mpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Full-tree MPC of run_math_model.py / math_model.py.

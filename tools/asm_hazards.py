@@ -5,7 +5,7 @@ VMEM instruction that reads that SGPR (the `saddr` base of the LDS-DMA and
 record loads).  CDNA needs 5 wait states there; with fewer the load may use
 the SGPR's previous value — a wrong address (measured: an illegal-address
 fault).
-    python tools/asm_hazards.py [file.s]     (default: compile mpc_rollout.hip)
+    python tools/asm_hazards.py [file.s]     (default: compile the library)
 Exit status 1 and one line per hazard if any is found."""
 import os
 import re
@@ -21,10 +21,16 @@ WAITS = 5
 
 
 def device_asm():
-    out = os.path.join(tempfile.mkdtemp(), "mpc_rollout.s")
-    subprocess.run([native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(REPO, "include"),
-                    "--cuda-device-only", "-S", "-o", out, native.SRC],
-                   check=True, capture_output=True, cwd=tempfile.gettempdir())
+    """The device assembly of every translation unit (native.SOURCES), one text."""
+    tmp = tempfile.mkdtemp()
+    out = os.path.join(tmp, "library.s")
+    with open(out, "w") as fh:
+        for src in native.SOURCES:
+            one = os.path.join(tmp, os.path.basename(src) + ".s")
+            subprocess.run([native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(REPO, "include"),
+                            "--cuda-device-only", "-S", "-o", one, src],
+                           check=True, capture_output=True, cwd=tempfile.gettempdir())
+            fh.write(open(one).read())
     return out
 
 

@@ -5,5 +5,5 @@
 set -e
 NAME=$1; shift
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ldl -ffp-contract=off \
-  -Wall -I include "$@" -o tools/var_$NAME.so diplomjourney_amd/csrc/mpc_rollout.hip
+  -Wall -I include "$@" -o tools/var_$NAME.so diplomjourney_amd/csrc/*.hip
 echo tools/var_$NAME.so

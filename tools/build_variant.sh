@@ -9,6 +9,6 @@ NAME=$1; REV=$2; shift 2
 D=$(mktemp -d)
 git archive "$REV" diplomjourney_amd/csrc include | tar -x -C "$D"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ldl -ffp-contract=off \
-  -I "$D/include" "$@" -o tools/var_$NAME.so "$D/diplomjourney_amd/csrc/mpc_rollout.hip"
+  -I "$D/include" "$@" -o tools/var_$NAME.so "$D"/diplomjourney_amd/csrc/*.hip
 rm -rf "$D"
 echo tools/var_$NAME.so

@@ -68,7 +68,7 @@ def build():
          f"  __syncthreads();\n  {b0(4)}\n  // Regular rotation-mode winner"),
     ])
     patch(os.path.join(cs, "mpc_argmin.h"), [
-        ("struct Rec {\n", f"__device__ uint64_t g_tl[8 * {NB} + 32];\n\nstruct Rec {{\n"),
+        ("struct Rec {\n", f"static __device__ uint64_t g_tl[8 * {NB} + 32];\n\nstruct Rec {{\n"),
     ])
     patch(os.path.join(cs, "mpc_finalize.h"), [
         ("  if (stage) s_head[threadIdx.x - 64] = head_word;\n",
@@ -144,7 +144,7 @@ def build():
     sys.path.insert(0, REPO)
     from diplomjourney_amd import native
     cmd = [native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(d, "include"), "-o", VAR,
-           os.path.join(cs, "mpc_rollout.hip")]
+           *[os.path.join(cs, os.path.basename(u)) for u in native.SOURCES]]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=d)
     shutil.rmtree(d)
     if r.returncode:

@@ -41,7 +41,7 @@ def build(src=None):
     mark = lambda q: f"if (threadIdx.x == 0) {{ const uint64_t tn = {NOW}; " \
                      f"tl_acc[{q}] += tn - tl_prev; tl_prev = tn; }}"   # noqa: E731
     patch(os.path.join(cs, "mpc_episodes.h"), [
-        ("constexpr int32_t kEpEnded", "__device__ uint64_t g_tl_ep[8 * 65536];\n\nconstexpr int32_t kEpEnded"),
+        ("constexpr int32_t kEpEnded", "static __device__ uint64_t g_tl_ep[8 * 65536];\n\nconstexpr int32_t kEpEnded"),
         ("  int64_t cands = 0;   // (thread 0)\n",
          "  int64_t cands = 0;   // (thread 0)\n  uint64_t tl_acc[6] = {0, 0, 0, 0, 0, 0};\n"
          f"  uint64_t tl_prev = {NOW};\n  int tl_n = 0;\n"),
@@ -73,7 +73,7 @@ def build(src=None):
     sys.path.insert(0, REPO)
     from diplomjourney_amd import native
     cmd = [native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(d, "include"), "-o", VAR,
-           os.path.join(cs, "mpc_rollout.hip")]
+           *[os.path.join(cs, os.path.basename(u)) for u in native.SOURCES]]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=d)
     shutil.rmtree(d)
     if r.returncode:

@@ -23,13 +23,22 @@ from diplomjourney_amd import native  # noqa: E402
 
 
 def device_asm(tree=REPO):
-    """Cross-compile the device pass with the product flags; the assembly goes
-    to a temporary directory outside the tree."""
-    out = os.path.join(tempfile.mkdtemp(), "mpc_rollout.s")
-    subprocess.run([native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(tree, "include"),
-                    "--cuda-device-only", "-S", "-o", out,
-                    os.path.join(tree, "diplomjourney_amd", "csrc", "mpc_rollout.hip")],
-                   check=True, capture_output=True, cwd=tempfile.gettempdir())
+    """Cross-compile the device pass of every translation unit the tree has
+    (native.SOURCES by name; an older revision may have fewer) with the product
+    flags; the assembly, one text, goes to a temporary directory outside the
+    tree."""
+    tmp = tempfile.mkdtemp()
+    out = os.path.join(tmp, "library.s")
+    with open(out, "w") as fh:
+        for src in native.SOURCES:
+            src = os.path.join(tree, "diplomjourney_amd", "csrc", os.path.basename(src))
+            if not os.path.exists(src):
+                continue
+            one = os.path.join(tmp, os.path.basename(src) + ".s")
+            subprocess.run([native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(tree, "include"),
+                            "--cuda-device-only", "-S", "-o", one, src],
+                           check=True, capture_output=True, cwd=tempfile.gettempdir())
+            fh.write(open(one).read())
     return out
 
 

@@ -10,7 +10,7 @@ sys.path.insert(0, REPO)
 from diplomjourney_amd import native  # noqa: E402
 
 cmd = [native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(REPO, "include"),
-       "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/resources_probe.so", native.SRC]
+       "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/resources_probe.so", *native.SOURCES]
 err = subprocess.run(cmd, capture_output=True, text=True, cwd="/tmp").stderr
 pat = re.compile(sys.argv[1]) if len(sys.argv) > 1 else None
 cur = None
