@@ -27,6 +27,10 @@
 // mpc_episodes_reset) carry the start, target and rules of each robot: the
 // run_math_model episodes (stop_rule 1, no events) and math_mpc episodes
 // (stop_rule 0, the operator schedule) can share one launch.
+//
+// Keep-out circles (mpc_episodes_run_obstacles) are the same kernel and the
+// same pair rollout with an obstacle hook (Obs; NoObs without circles); the
+// hooks of the modes: mpc_episodes_obs.h.
 #pragma once
 
 #include "mpc_argmin.h"
@@ -82,22 +86,33 @@ __global__ void k_episodes_reset(const mpc_episode_config_t* __restrict__ cfgs, 
 // NS > 0: the horizon as a compile-time constant (the reference's N = 3):
 // the loop unrolls, and the steps' sin/cos — which depend only on the heading
 // chain, a sum of the candidate's constant increment — overlap.
-template <int INTEG, int ROT, bool PL2, int NS = 0>
+// Obs: the obstacle hook of the rollout lanes (mpc_device.h: NoObs, the
+// default, instantiates no obstacle statement; CircleObs / FrameObs test
+// circles).  Two `blocked` flags sit next to `bad`; ONE loop<2> call after each
+// step of the pair reads the table once for both candidates (the unrolled
+// horizon and the generic one alike); a flagged candidate's recompute resets
+// its flag and tests every step_safe state against the world table.
+// blocked_out[2] (Obs::kOn only).
+template <int INTEG, int ROT, bool PL2, int NS = 0, class Obs = NoObs>
 __device__ __forceinline__ void const_pair_cost_l(const Consts& K, const double (&v)[2],
                                                   const double (&b)[2], int n_steps,
-                                                  double (&cst)[2]) {
+                                                  double (&cst)[2], const Obs& obs = Obs{},
+                                                  bool* blocked_out = nullptr) {
   if constexpr (NS > 0) n_steps = NS;
   double x[2], y[2], ph[2], s[2], c[2];
   bool bad[2];
+  [[maybe_unused]] bool blocked[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     step_start<ROT>(K, x[j], y[j], ph[j], s[j], c[j]);
     bad[j] = false;
+    if constexpr (Obs::kOn) blocked[j] = false;
   }
   auto one_step = [&]() {
 #pragma unroll
     for (int j = 0; j < 2; ++j)
       step_core<INTEG, ROT, PL2>(x[j], y[j], ph[j], s[j], c[j], v[j], b[j], K, bad[j]);
+    if constexpr (Obs::kOn) obs.template loop<2>(x, y, blocked);
   };
   if constexpr (NS > 0) {
 #pragma unroll
@@ -114,20 +129,26 @@ __device__ __forceinline__ void const_pair_cost_l(const Consts& K, const double 
       x[j] = K.x;
       y[j] = K.y;
       ph[j] = K.phi;
-      for (int st = 0; st < n_steps; ++st) step_safe<INTEG>(x[j], y[j], ph[j], v[j], b[j], K);
+      if constexpr (Obs::kOn) blocked[j] = false;   // the recompute's states replace the loop's
+      for (int st = 0; st < n_steps; ++st) {
+        step_safe<INTEG>(x[j], y[j], ph[j], v[j], b[j], K);
+        if constexpr (Obs::kOn) obs.world(x[j], y[j], blocked[j]);
+      }
     }
     cst[j] = cost(x[j], y[j], K);
+    if constexpr (Obs::kOn) blocked_out[j] = blocked[j];
   }
 }
 
-template <int INTEG, int ROT, int NS = 0>
+template <int INTEG, int ROT, int NS = 0, class Obs = NoObs>
 __device__ __forceinline__ void const_pair_cost(const Consts& K, const double (&v)[2],
                                                 const double (&b)[2], int n_steps,
-                                                double (&cst)[2]) {
+                                                double (&cst)[2], const Obs& obs = Obs{},
+                                                bool* blocked_out = nullptr) {
   if (K.L_pow2)
-    const_pair_cost_l<INTEG, ROT, true, NS>(K, v, b, n_steps, cst);
+    const_pair_cost_l<INTEG, ROT, true, NS, Obs>(K, v, b, n_steps, cst, obs, blocked_out);
   else
-    const_pair_cost_l<INTEG, ROT, false, NS>(K, v, b, n_steps, cst);
+    const_pair_cost_l<INTEG, ROT, false, NS, Obs>(K, v, b, n_steps, cst, obs, blocked_out);
 }
 
 // The step's winner (constant controls v, b) re-derived by ONE lane with the
@@ -246,6 +267,25 @@ __device__ inline void wave_winner_states_l(const Consts& K, double v, double b,
     }
 }
 
+// The block's sum of the lanes' counts, valid in thread 0 (every thread of the
+// block calls it).
+__device__ __forceinline__ int64_t block_sum_i64(int64_t n) {
+  __shared__ int64_t s_part[kWaves];
+  uint64_t sum = static_cast<uint64_t>(n);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {   // (two 32-bit halves: no carry between lanes' words)
+    const uint32_t lo = __shfl_xor(static_cast<int>(static_cast<uint32_t>(sum)), off, 64);
+    const uint32_t hi = __shfl_xor(static_cast<int>(static_cast<uint32_t>(sum >> 32)), off, 64);
+    sum += (static_cast<uint64_t>(hi) << 32) | lo;
+  }
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = static_cast<int64_t>(sum);
+  __syncthreads();
+  int64_t all = 0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < kWaves; ++w) all += s_part[w];
+  return all;
+}
+
 // Block r = robot r (kBlock threads): up to max_calls MPC steps of its episode
 // (fewer if it ends).  log: [n][cap] ring per robot; progress (optional):
 // {calls, stop, candidates} per robot after the launch.
@@ -256,11 +296,32 @@ __device__ inline void wave_winner_states_l(const Consts& K, double v, double b,
 // (grid, re-roll, update: one wave or one lane) share their SIMD with the
 // other resident robot's waves.  (One candidate at a time, and one wave per
 // robot, were measured and not kept: DESIGN.md §1 and §6f.)
-template <int INTEG, int ROT>
+//
+// With keep-out circles (mpc_episodes_run_obstacles; Obs = the mode's hook,
+// mpc_episodes_obs.h) the kernel has two arguments more, through the packs:
+// world (W = Obstacles), the one circle table of the launch, kernel argument 0
+// (read through kernarg_world(): scalar loads), and count (B = int64_t; NULL:
+// not counted), the last argument: [n] per robot the candidates blocked in
+// the steps this launch ran for it (0 if none ran), written beside
+// progress[r] by thread 0 — a lane-private add per pair, one block reduction
+// at the end of the launch, no atomic.  (B* __restrict__: a pack deduced as
+// B... would drop the qualifier, and hipcc then loads the argument elsewhere.)
+// The semantics are mpc_rollout_partials_obstacles'
+// (include/mpc_rollout.h): a blocked candidate never wins, an all-blocked step
+// is the step without a finite cost (index -1, found 0, a stale step).  Every
+// circle statement sits under `if constexpr (Obs::kOn)` in this one body: the
+// plain instantiations (NoObs, empty packs) compile to what they were before
+// the circles came (tools/kernel_digest.py).
+// The hook is made by episode_obs(Obs*), found by argument-dependent lookup
+// where the kernel is instantiated: this header, which the host replica's
+// build parses, does not see FrameObs and the chained kernels it pulls in.
+template <int INTEG, int ROT, class Obs = NoObs, class... W, class... B>
 __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
-    const mpc_episode_config_t* __restrict__ cfgs, RobotState* __restrict__ robots, int n_steps,
-    int max_calls, mpc_episode_log_t* __restrict__ log, int cap,
-    mpc_episodes_progress_t* __restrict__ progress) {
+    W... world, const mpc_episode_config_t* __restrict__ cfgs, RobotState* __restrict__ robots,
+    int n_steps, int max_calls, mpc_episode_log_t* __restrict__ log, int cap,
+    mpc_episodes_progress_t* __restrict__ progress, B* __restrict__... count) {
+  static_assert(sizeof...(W) == (Obs::kOn ? 1 : 0) && sizeof...(B) == sizeof...(W),
+                "the table and the count come with a hook, and only with one");
   const int r = blockIdx.x;
   const mpc_episode_config_t& c = cfgs[r];
   RobotState* __restrict__ R = &robots[r];
@@ -278,7 +339,14 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
     s_stop = R->stop;
     s_calls = R->calls;
   }
-  int64_t cands = 0;   // (thread 0)
+  [[maybe_unused]] Obs obs = [] {   // (FrameObs: its world table; the frame table per step)
+    if constexpr (Obs::kOn)
+      return episode_obs(static_cast<Obs*>(nullptr));
+    else
+      return Obs{};
+  }();
+  int64_t cands = 0;                    // (thread 0)
+  [[maybe_unused]] int64_t n_blk = 0;   // this lane's blocked candidates
   for (int call = 0; call < max_calls; ++call) {
     __syncthreads();
     if (s_stop) break;   // uniform
@@ -293,6 +361,9 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
     }
     __syncthreads();
     const Consts K = uniform_consts(Hs->K);
+    // rect+cum: the circles in the frame of THIS step's sums (uniform: the whole
+    // block is here; the table's last readers passed the barriers above)
+    if constexpr (Obs::kOn && ROT == kRotCum) obs.form(K, K.L_pow2 != 0);
     const double incumbent = Hs->incumbent;
     const int nv = s_nv, nb = s_nb, n_grid = nv * nb;
     uint64_t best_k = ~0ull;
@@ -302,20 +373,33 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
     for (int k0 = threadIdx.x; k0 < n_grid; k0 += 2 * kBlock) {
       const int k1 = k0 + kBlock;
       const bool has1 = k1 < n_grid;
-      const int kq = has1 ? k1 : k0;   // (a valid stand-in; its cost is not used)
+      const int kq = has1 ? k1 : k0;   // (a valid stand-in: neither wins nor is counted)
       const double vv[2] = {s_v[k0 / nb], s_v[kq / nb]};
       const double bb[2] = {s_b[k0 % nb], s_b[kq % nb]};
       double cst[2];
+      [[maybe_unused]] bool blk[2];
       if (n_steps == 3)   // uniform: the reference's horizon, unrolled
-        const_pair_cost<INTEG, ROT, 3>(K, vv, bb, n_steps, cst);
+        const_pair_cost<INTEG, ROT, 3, Obs>(K, vv, bb, n_steps, cst, obs, blk);
       else
-        const_pair_cost<INTEG, ROT>(K, vv, bb, n_steps, cst);
-      uint64_t kk = cost_key_nonneg(cst[0]);
+        const_pair_cost<INTEG, ROT, 0, Obs>(K, vv, bb, n_steps, cst, obs, blk);
+      if constexpr (Obs::kOn) {
+        blk[1] = has1 && blk[1];
+        n_blk += static_cast<int>(blk[0]) + static_cast<int>(blk[1]);
+      }
+      // (a blocked candidate: the key of a non-finite cost, which never wins)
+      uint64_t kk;
+      if constexpr (Obs::kOn)
+        kk = blk[0] ? ~0ull : cost_key_nonneg(cst[0]);
+      else
+        kk = cost_key_nonneg(cst[0]);
       if (kk < best_k) {
         best_k = kk;
         best_i = k0;
       }
-      kk = cost_key_nonneg(cst[1]);
+      if constexpr (Obs::kOn)
+        kk = blk[1] ? ~0ull : cost_key_nonneg(cst[1]);
+      else
+        kk = cost_key_nonneg(cst[1]);
       if (has1 && kk < best_k) {
         best_k = kk;
         best_i = k1;
@@ -393,6 +477,12 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
   __syncthreads();
   for (int q = threadIdx.x; q < kStoredWords; q += kBlock)
     reinterpret_cast<uint64_t*>(R)[q] = s_head[q];
+  [[maybe_unused]] int64_t* n_blocked = nullptr;
+  [[maybe_unused]] int64_t blocked_all = 0;
+  if constexpr (Obs::kOn) {
+    n_blocked = (count, ...);
+    if (n_blocked) blocked_all = block_sum_i64(n_blk);   // (uniform: a kernel argument)
+  }
   if (threadIdx.x == 0) {
     R->stop = s_stop;
     R->calls = s_calls;
@@ -401,6 +491,9 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       progress[r].calls = s_calls;
       progress[r].stop = s_stop;
       progress[r].candidates = R->candidates;
+    }
+    if constexpr (Obs::kOn) {
+      if (n_blocked) n_blocked[r] = blocked_all;
     }
   }
 }

@@ -1,8 +1,8 @@
 // mpc_episodes_obs.hip — the second translation unit of libmpc_rollout.so: the
-// batched robots' episode kernel with keep-out circles (mpc_episodes_obs.h)
-// and its launch.  The entry, its checks and the plain kernel stay in
-// mpc_rollout.hip (episodes_run); why the kernels are compiled apart:
-// mpc_episodes_obs_launch.h.
+// circle instantiations of the batched robots' episode kernel (k_episodes_run,
+// mpc_episodes.h, with the hooks of mpc_episodes_obs.h) and their launch.  The
+// entry, its checks and the plain instantiations stay in mpc_rollout.hip
+// (episodes_run); why the two are compiled apart: mpc_episodes_obs_launch.h.
 // (the headers' plain, non-template kernels are mpc_rollout.hip's: one definition
 // per library)
 #define MPC_TEMPLATES_ONLY
@@ -19,7 +19,7 @@ void launch_episodes_run_obs(hipStream_t st, int32_t integrator, const Obstacles
                              mpc_episodes_progress_t* progress, int64_t* n_blocked) {
   dispatch_mode(integrator, [&](auto I, auto R) {
     dispatch_nobs<true>(n_obs, [&](auto NOBS) {
-      k_episodes_run_obs<I, R, NOBS><<<n_robots, kBlock, 0, st>>>(
+      k_episodes_run<I, R, EpisodesObs<R, NOBS>, Obstacles><<<n_robots, kBlock, 0, st>>>(
           world, cfgs, robots, n_steps, max_calls, log, cap, progress, n_blocked);
     });
   });

@@ -87,6 +87,7 @@ class RobotModel(EM.EpisodeModel):
             states, costs = harness.replica_rollout(prob, v, b, self.integ, device_consts=True)
         else:
             states, costs = np.empty((self.n_steps, 3, 0)), np.empty(0)
+        costs = self.score(states, costs, v, b)
         row = winner(states, costs, v, b)
         self.last = (costs, row)
         self.ties.append(int((costs == row.cost).sum()) if row.index >= 0 else 0)
@@ -96,6 +97,11 @@ class RobotModel(EM.EpisodeModel):
         self.calls += 1
         self.candidates += n_grid
         return rec
+
+    def score(self, states, costs, v, b):
+        """The costs the winner is chosen from, given the rollout's (a subclass
+        overrides this: robots_obstacle_model blocks candidates here)."""
+        return costs
 
     def to_robot(self):
         """RobotState.  h.nv and h.nb: k_episodes_run keeps its grid in LDS and
@@ -111,13 +117,14 @@ class RobotModel(EM.EpisodeModel):
         return MpcEpisodesProgress(calls=self.calls, stop=self.stop, candidates=self.candidates)
 
 
-def run(cfgs, n_steps, integ, max_calls, device=False):
-    """Every robot's model run for up to max_calls steps, in lockstep (robots
-    do not interact: the order is free).  Per step ONE table of reciprocal
-    estimates for the union of the running robots' B grids (device=True: the
-    GPU's; False: the host's 1.0 / q) and no miss.  Returns (models, records
-    per robot, first-step costs per robot)."""
-    models = [RobotModel(c, n_steps, integ) for c in cfgs]
+def run(cfgs, n_steps, integ, max_calls, device=False, model=RobotModel):
+    """Every robot's model — model(cfg, n_steps, integ): RobotModel or a factory
+    of a subclass — run for up to max_calls steps, in lockstep (robots do not
+    interact: the order is free).  Per step ONE table of reciprocal estimates
+    for the union of the running robots' B grids (device=True: the GPU's;
+    False: the host's 1.0 / q) and no miss.  Returns (models, records per
+    robot, first-step (costs, Result) per robot)."""
+    models = [model(c, n_steps, integ) for c in cfgs]
     recs = [[] for _ in models]
     first = [None] * len(models)
     for call in range(max_calls):

@@ -1,7 +1,7 @@
 """One robot of the batched device episodes with keep-out circles
-(k_episodes_run_obs, csrc/mpc_episodes_obs.h) restated on the host:
-robots_model.RobotModel with one statement more per step.  The step's states
-are the replica's; the mask is ranking.blocked of them (the header's formula
+(k_episodes_run with an obstacle hook, csrc/mpc_episodes.h) restated on the
+host: robots_model.RobotModel with its `score` step overridden.  The step's
+states are the replica's; the mask is ranking.blocked of them (the header's formula
 in world coordinates: any step-end state 1..N strictly inside any circle, a
 NaN state inside nothing); blocked costs become +inf, and robots_model.winner
 and the update run unchanged, so an all-blocked step is the step without a
@@ -16,7 +16,6 @@ import math
 
 import numpy as np
 
-import harness
 import ranking
 import robots_model as RM
 
@@ -31,19 +30,12 @@ class ObstacleRobotModel(RM.RobotModel):
         self.free = []            # per step: the winner without circles (index; -1: none)
         self.poses = []           # per step: the pose it started from
 
-    def mpc_step(self):
-        """RobotModel.mpc_step with the mask between the rollout and the
-        winner (a change to either belongs in both)."""
-        if self.stop:
-            return None
-        V, B, _ = self.grids()
-        n_grid = len(V) * len(B)
-        self.sizes.append((len(V), len(B)))
+    def score(self, states, costs, v, b):
+        """The blocked candidates' costs +inf (RobotModel.mpc_step calls this
+        between the rollout and the winner, before the pose moves)."""
+        n_grid = len(costs)
         self.poses.append((self.x, self.y))
-        prob, _ = self.begin_step()
-        v, b = RM.enumerate_controls(V, B, self.n_steps)
         if n_grid:
-            states, costs = harness.replica_rollout(prob, v, b, self.integ, device_consts=True)
             mask, margin = ranking.blocked(states, self.circles)
             early = (ranking.blocked(states[:-1], self.circles)[0] if self.n_steps > 1
                      else np.zeros(n_grid, dtype=bool))
@@ -54,21 +46,11 @@ class ObstacleRobotModel(RM.RobotModel):
             if margin == margin:                  # (NaN: no finite state at all)
                 self.margin = min(self.margin, margin)
         else:
-            states, costs = np.empty((self.n_steps, 3, 0)), np.empty(0)
             mask = early = np.zeros(0, dtype=bool)
         self.free.append(RM.winner(states, costs, v, b).index)
-        costs = np.where(mask, math.inf, costs)
-        row = RM.winner(states, costs, v, b)
-        self.last = (costs, row)
         self.masks.append((mask, early))
         self.blocked_steps.append(int(mask.sum()))
-        self.ties.append(int((costs == row.cost).sum()) if row.index >= 0 else 0)
-        rec = self.advance([row], restart=False)
-        if rec["status"] & RM.EP_ENDED:
-            self.stop = rec["status"]
-        self.calls += 1
-        self.candidates += n_grid
-        return rec
+        return np.where(mask, math.inf, costs)
 
     def blocked_in(self, first, last):
         """The blocked candidates of steps [first, last)."""
@@ -78,22 +60,8 @@ class ObstacleRobotModel(RM.RobotModel):
 def run(cfgs, n_steps, integ, max_calls, circles, fillers=(), device=False):
     """robots_model.run with ObstacleRobotModel (one table for all robots).
     Returns (models, records per robot, first-step (costs, Result) per robot)."""
-    models = [ObstacleRobotModel(c, n_steps, integ, circles, fillers) for c in cfgs]
-    recs = [[] for _ in models]
-    first = [None] * len(models)
-    for call in range(max_calls):
-        live = [(r, M) for r, M in enumerate(models) if not M.stop]
-        if not live:
-            break
-        betas = np.unique(np.concatenate([np.array(M.grids()[1], dtype=np.float64)
-                                          for _, M in live]))
-        with harness.estimates_installed(betas, device) as misses:
-            for r, M in live:
-                recs[r].append(M.mpc_step())
-                if call == 0:
-                    first[r] = M.last
-            assert misses() == 0, f"step {call}: a denominator without its device estimate"
-    return models, recs, first
+    return RM.run(cfgs, n_steps, integ, max_calls, device=device,
+                  model=lambda c, n, i: ObstacleRobotModel(c, n, i, circles, fillers))
 
 
 def launch_counts(models, launches):

@@ -1,6 +1,6 @@
 """Keep-out circles in the batched robots' device-resident episodes
-(mpc_episodes_run_obstacles, k_episodes_run_obs in csrc/mpc_episodes_obs.h,
-through DeviceEpisodes) pinned to the host model, bit for bit.
+(mpc_episodes_run_obstacles, k_episodes_run with an obstacle hook in
+csrc/mpc_episodes.h, through DeviceEpisodes) pinned to the host model, bit for bit.
 
 Every comparison is robots_model.compare on the whole state tensor, every log
 ring and the progress records — `==` on the bits — plus read_blocked() ==
