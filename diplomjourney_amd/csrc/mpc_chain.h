@@ -22,6 +22,7 @@
 #include "mpc_finalize.h"
 #include "mpc_kernels.h"
 #include "mpc_lanes.h"
+#include "mpc_timeline.h"
 #include "mpc_winner.h"
 
 namespace mpc {
@@ -53,6 +54,7 @@ namespace mpc {
 // part, the next launch's block 0 reduces them) with the per-rank candidates
 // exchanged through the mailboxes by block 0 (p2p_complete).
 constexpr int kChainFin = 1, kChainXchg = 3, kChainP2P = 4;
+TL_BOUND(kChainBlocks, kMaxBlocks + 1);   // a chained grid: block 0 + rollout_grid() tile blocks
 
 // LDS dwords (Consts layout) -> wave-uniform Consts, field by field (no
 // memory view of the struct: it stays in SGPRs).
@@ -149,6 +151,7 @@ __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32
                                             int n_steps, Rec* __restrict__ part, int has_prev,
                                             const mpc_episode_config_t& ecfg, Obs obs = Obs{},
                                             unsigned long long* __restrict__ n_blocked = nullptr) {
+  TL_TILE(0);
   constexpr int CPL = 2;
   __shared__ __attribute__((aligned(16))) uint32_t s_w[kPubWords];
   __shared__ uint32_t s_tag[kPubWords];
@@ -177,6 +180,7 @@ __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32
       if (threadIdx.x == 0) s_final = fin;
     }
     __syncthreads();
+    TL_TILE(1);
     Kl = consts_from_words(s_w);
     if constexpr (Obs::kOn) return;   // (first(), below: waits instead of speculating)
     if (s_final) return;
@@ -252,6 +256,7 @@ __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32
       }
       __syncthreads();
     }
+    TL_TILE(2);
   };
   // What the lane calls once its first control loads are in flight.
   auto first = [&]() {
@@ -307,12 +312,15 @@ __device__ __forceinline__ void chain_tiles(EpisodeState* __restrict__ S, uint32
     }
   }
   if constexpr (Obs::kOn) store_wave_blocked(wave_blocked);
+  TL_TILE(4);
   block_argmin<true>(best_k, best_i);   // (indices < n_cand < 2^31)
+  TL_TILE(5);
   if (threadIdx.x == 0) {
     if constexpr (TAGGED)
       store_tagged_rec(&part[blockIdx.x - 1], best_k, best_i, epoch);
     else
       part[blockIdx.x - 1] = Rec{best_k, best_i};
+    TL_TILE_STORED(3);
   }
   if constexpr (Obs::kOn) add_block_blocked(n_blocked);
 }
@@ -328,6 +336,7 @@ __global__ __launch_bounds__(kBlock, chain_waves<MODE>()) void k_episode_chain(
     uint32_t wait_tag) {
   static_assert(ROT == kRotCum, "chained steps need the pose-independent recurrence");
   if (blockIdx.x == 0) {
+    TL_TILE(0);
     if (has_prev) {
       // the completion of step k-1 publishes step k's constants itself, from
       // its LDS copy of the updated head (store_update)

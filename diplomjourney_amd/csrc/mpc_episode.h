@@ -22,6 +22,7 @@
 
 #include "../../include/mpc_rollout.h"
 #include "mpc_device.h"
+#include "mpc_timeline.h"
 #include "mpc_winner.h"
 
 namespace mpc {
@@ -299,6 +300,7 @@ __device__ inline void episode_advance(const mpc_episode_config_t& c, EpisodeHea
                                        StaleTraj& st, const Winner& r, mpc_episode_log_t& L,
                                        const uint32_t* early = nullptr,
                                        bool* early_bad = nullptr) {
+  TL_B0(9);
   EpisodeHead* S = &H;
   S->steps_for_slowing -= 1;
   S->incumbent = 9223372036854775808.0;  // float(sys.maxsize), :428
@@ -343,6 +345,7 @@ __device__ inline void episode_advance(const mpc_episode_config_t& c, EpisodeHea
     const double ex = S->x_t - st.ot[2][0], ey = S->y_t - st.ot[2][1];
     if (ex * ex + ey * ey <= c.eps) S->m += 1;
   }
+  TL_B0(10);
   const double x_prev = S->x, y_prev = S->y;   // x_previous / y_previous (:570-571)
   S->x = st.ot[k][0];   // (st lives in LDS: a dynamic index is an LDS address)
   S->y = st.ot[k][1];
@@ -405,10 +408,12 @@ __device__ inline void episode_advance(const mpc_episode_config_t& c, EpisodeHea
   L.v = S->v;
   L.beta = S->beta;
   L.status = status;
+  TL_B0(6);
   if (ended) {
     if constexpr (!RESTART) return;
     episode_restart(c, *S);
   }
+  TL_B0(11);
   if (early && (ended || reinterpret_cast<const Consts*>(early)->x != S->x ||
                 reinterpret_cast<const Consts*>(early)->y != S->y ||
                 reinterpret_cast<const Consts*>(early)->phi != S->phi))
@@ -420,6 +425,7 @@ __device__ inline void episode_advance(const mpc_episode_config_t& c, EpisodeHea
   } else {
     episode_prepare(c, *S);
   }
+  TL_B0(12);
 }
 
 __device__ void episode_hook(const mpc_episode_config_t& c, const EpisodeHook& h,

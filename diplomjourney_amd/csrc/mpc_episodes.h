@@ -38,6 +38,7 @@
 #include "mpc_episode.h"
 #include "mpc_generated.h"
 #include "mpc_lanes.h"
+#include "mpc_timeline.h"
 #include "mpc_winner.h"
 
 namespace mpc {
@@ -54,6 +55,8 @@ struct RobotState {
 static_assert(offsetof(RobotState, st) == sizeof(EpisodeHead), "stale trajectory follows the head");
 
 constexpr int32_t kEpEnded = MPC_EP_ARRIVED | MPC_EP_BREAK | MPC_EP_LIMIT;
+constexpr int32_t kEpMaxRobots = 65535;   // robots of one launch (one block each; the entries refuse more)
+TL_BOUND(kRobots, kEpMaxRobots);
 
 // The state of n robots: RobotState[n], then each robot's configuration
 // (mpc_episodes_reset copies them in), so a run needs nothing but the state.
@@ -347,9 +350,11 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
   }();
   int64_t cands = 0;                    // (thread 0)
   [[maybe_unused]] int64_t n_blk = 0;   // this lane's blocked candidates
+  TL_EP_BEGIN();
   for (int call = 0; call < max_calls; ++call) {
     __syncthreads();
     if (s_stop) break;   // uniform
+    TL_EP_CALL();
     const EpisodeHead* Hs = reinterpret_cast<const EpisodeHead*>(s_head);
     if (threadIdx.x < 64) {
       int nv, nb;
@@ -360,6 +365,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       }
     }
     __syncthreads();
+    TL_EP_MARK(0);
     const Consts K = uniform_consts(Hs->K);
     // rect+cum: the circles in the frame of THIS step's sums (uniform: the whole
     // block is here; the table's last readers passed the barriers above)
@@ -405,6 +411,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
         best_i = k1;
       }
     }
+    TL_EP_MARK(1);
     block_argmin<true>(best_k, best_i);
     if (threadIdx.x == 0) {
       s_bk = best_k;
@@ -412,6 +419,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       cands += n_grid;
     }
     __syncthreads();
+    TL_EP_MARK(2);
     const uint64_t bk = s_bk;
     const int64_t bi = s_bi;
     // (in LDS: thread 0's private copy spilled to scratch, a memory round
@@ -460,6 +468,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       emit_winner<INTEG, ROT>(K, lds.pv, lds.pb, 1, n_steps, bk, bi, bi, incumbent, &s_out,
                               &lds, &win, lds.pv, lds.pb, false);
     }
+    TL_EP_MARK(3);
     if (threadIdx.x == 0) {   // (emit_winner, if it ran, ended with a barrier)
       EpisodeHead H;
       __builtin_memcpy(&H, s_head, sizeof(EpisodeHead));
@@ -469,10 +478,12 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       if (s_log.status & kEpEnded) s_stop = s_log.status;
       s_calls += 1;
     }
+    TL_EP_MARK(4);
     __syncthreads();
     if (log && cap > 0 && threadIdx.x < kLogWords)
       reinterpret_cast<uint64_t*>(&log[static_cast<int64_t>(r) * cap + s_log.step % cap])
           [threadIdx.x] = reinterpret_cast<const uint64_t*>(&s_log)[threadIdx.x];
+    TL_EP_MARK(5);
   }
   __syncthreads();
   for (int q = threadIdx.x; q < kStoredWords; q += kBlock)
@@ -496,6 +507,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       if (n_blocked) n_blocked[r] = blocked_all;
     }
   }
+  TL_EP_END();
 }
 
 }  // namespace mpc

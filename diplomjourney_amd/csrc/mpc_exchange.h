@@ -24,6 +24,7 @@
 #include "mpc_finalize.h"
 #include "mpc_kernels.h"
 #include "mpc_lanes.h"
+#include "mpc_timeline.h"
 #include "mpc_winner.h"
 
 namespace mpc {
@@ -156,6 +157,7 @@ __device__ void advance_from_candidates(const mpc_episode_config_t& c, EpisodeSt
   // publishes the next step's constants (a chained exchange step's block 0)
   store_update(&S->h, s_head, s_slot, reinterpret_cast<const uint64_t*>(&s_log), S->chain_pub,
                kPubWords, publish_epoch);
+  TL_B0(8);
   emit_winner_tail<INTEG, ROT>(K, w->n_steps, lds, out);   // the rest of the record
 }
 
@@ -602,6 +604,7 @@ __device__ void p2p_complete(const mpc_episode_config_t& c, EpisodeState* S, voi
   mpc_candidate_t* lc = cand_lds();
   records_candidate<TILED>(part_prev, n_part_prev, v_prev, b_prev, n_cand, n_steps, index_base,
                            lc);
+  TL_B0(1);
   if (static_cast<int>(threadIdx.x) < world) s_peers[threadIdx.x] = my_peer;
   if (threadIdx.x == 0) {
     s_rank = my_rank;
@@ -611,8 +614,10 @@ __device__ void p2p_complete(const mpc_episode_config_t& c, EpisodeState* S, voi
   __syncthreads();
   const uint32_t slot = s_seq & 1u;
   post_candidate(s_peers, s_rank, world, prev, slot, n_steps, lc);
+  TL_B0(2);
   const mpc_candidate_t* g =
       wait_mailbox(S, mb, prev, slot, world, n_steps, s_err == 5u ? 0ull : kPeerWaitTicks);
+  TL_B0(3);
   if (threadIdx.x == 0) S->p2p_seq = s_seq + 1u;   // read by the next launch
   if (g) {
     advance_from_candidates<INTEG, ROT>(c, S, g, world, out_prev, log, cap, publish_epoch,

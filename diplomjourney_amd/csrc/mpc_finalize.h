@@ -21,6 +21,7 @@
 #include "mpc_device.h"
 #include "mpc_episode.h"
 #include "mpc_lanes.h"
+#include "mpc_timeline.h"
 #include "mpc_winner.h"
 
 namespace mpc {
@@ -200,6 +201,7 @@ __device__ __forceinline__ void finalize_block(
         i = r[q].idx;
       }
   }
+  TL_B0(1);
   if (stage) s_head[threadIdx.x - 64] = head_word;
   // record indices are local candidate indices: below 2^31 for any row the
   // candidate arrays can hold in practice -> three 32-bit DPP minima
@@ -207,6 +209,7 @@ __device__ __forceinline__ void finalize_block(
     wave_argmin32(k, i);
   else
     wave_argmin(k, i);
+  TL_B0(2);
   // Each wave's best candidate's controls, loaded while the waves' minima are
   // combined: the block's winner is one of them, so its re-roll starts
   // without a dependent load of its own (one memory round trip fewer on the
@@ -229,6 +232,7 @@ __device__ __forceinline__ void finalize_block(
   __syncthreads();
   // every thread forms the block's winner (thread 0's result as before), so
   // the wave that holds it knows to stage its controls
+  TL_B0(3);
   int wbest = 0;
   k = s_key[0];
   i = s_idx[0];
@@ -301,6 +305,7 @@ __device__ __forceinline__ void finalize_block(
         Kp.phi = ph;
       }
       __hip_atomic_store(&s_pose, ok ? 1 : 2, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      TL_B0_IF(true, 19);
     };
     auto side_b = [&](bool fast) {
       const int q = threadIdx.x;
@@ -325,6 +330,7 @@ __device__ __forceinline__ void finalize_block(
         if (q == 64)   // (the wave's three LDS stores are in order before it)
           __hip_atomic_store(&s_sc_ready, all_in ? 1 : 2, __ATOMIC_RELEASE,
                              __HIP_MEMORY_SCOPE_WORKGROUP);
+        TL_B0_IF(q == 64, 18);
       }
       if (early_on && q >= 192 && q < 256) {   // wave 3: the pick's last part, the publication
         if (q == 192) {
@@ -371,11 +377,13 @@ __device__ __forceinline__ void finalize_block(
           __hip_atomic_store(&hook.chain_pub[w3],
                              (static_cast<uint64_t>(s_pub[w3]) << 32) | hook.publish_epoch,
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        TL_B0_IF(q == 192, 13);
       }
     };
     emit_winner<INTEG, ROT>(K, v, b, n_cand, n_steps, k, i, index_base + i, incumbent, out, lds,
                             &w, s_pv, s_pb, KDEV && hook.H, side_a, side_b, on_layer);
   }
+  TL_B0(5);
   if (KDEV && hook.H) {
     const bool early = hook.publish_epoch && s_early;   // (uniform)
     if (threadIdx.x == 0) {
@@ -386,6 +394,7 @@ __device__ __forceinline__ void finalize_block(
       episode_hook(ecfg, hook, w, *reinterpret_cast<EpisodeHead*>(s_head),
                    *reinterpret_cast<StaleTraj*>(&s_head[kHeadWords]), s_log, s_slot,
                    early ? s_pub : nullptr, &bad);
+      TL_B0(7);
       if (bad && hook.chain_error) *hook.chain_error = 6u;
     }
     __syncthreads();
@@ -396,13 +405,16 @@ __device__ __forceinline__ void finalize_block(
       episode_early_prepare(ecfg, *reinterpret_cast<const EpisodeHead*>(s_head),
                             *reinterpret_cast<const StaleTraj*>(&s_head[kHeadWords]), E);
       *reinterpret_cast<EarlyPub*>(reinterpret_cast<uint64_t*>(hook.H) + kStoredWords) = E;
+      TL_B0_IF(true, 15);
     }
     // the head and the log record back to HBM, the chain tags cleared (or the
     // next step's constants published, unless they already are)
     store_update(hook.H, s_head, s_slot, reinterpret_cast<const uint64_t*>(&s_log),
                  hook.chain_pub, hook.chain_pub_words, hook.publish_epoch, early, s_pub);
+    TL_B0(8);
     // the record's remaining trajectory, off the update's critical path
     emit_winner_tail<INTEG, ROT>(K, n_steps, lds, out);
+    TL_B0(14);
   }
 }
 

@@ -13,6 +13,7 @@
 
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -462,8 +463,8 @@ int episodes_run(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacl
                  mpc_episode_log_t* log, int32_t log_capacity, mpc_episodes_progress_t* progress,
                  int64_t* n_blocked_out, mpc_stream_t stream) {
   if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
-  if (!state || n_robots < 1 || n_robots > 65535 || n_steps < 1 || n_steps > MPC_MAX_STEPS ||
-      max_calls < 0 || log_capacity < 0 || (log && log_capacity < 1))
+  if (!state || n_robots < 1 || n_robots > kEpMaxRobots || n_steps < 1 ||
+      n_steps > MPC_MAX_STEPS || max_calls < 0 || log_capacity < 0 || (log && log_capacity < 1))
     return MPC_ERR_ARG;
   if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
   if (max_calls == 0) return MPC_OK;
@@ -940,15 +941,32 @@ int mpc_episode_chain_step_obstacles(
                             beta_prev, out_prev, log, log_capacity, n_blocked_out, stream);
 }
 
-#ifdef MPC_RUN_STATS
-int mpc_debug_run_stats(unsigned long long* host, int reset) {
-  if (reset) {
-    unsigned long long init[kRunMaxSteps][8];
-    for (int j = 0; j < kRunMaxSteps; ++j)
-      for (int f = 0; f < 8; ++f) init[j][f] = (f == 3) ? ~0ull : 0ull;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_run_tl), init, sizeof(init)) == hipSuccess ? 0 : -1;
+#ifdef MPC_TIMELINE
+// Variant builds only (-DMPC_TIMELINE; not in include/mpc_rollout.h: tools/timeline.py
+// binds it): the stamp tables of mpc_timeline.h.  which: 0 the chained step's
+// (g_tl), 1 workload R's (g_tl_ep), 2 the persistent run's (g_run_tl).  reset:
+// the table back to its rest values (zero; the run's min field all ones), dst
+// unused; else its first `bytes` bytes into dst (more than the table: an error).
+int mpc_debug_timeline(int which, void* dst, size_t bytes, int reset) {
+  if (which < 0 || which > 2) return MPC_ERR_ARG;
+  // (the symbols by address: the runtime's untyped overloads)
+  const void* sym = which == 0 ? static_cast<const void*>(&g_tl)
+                    : which == 1 ? static_cast<const void*>(&g_tl_ep)
+                                 : static_cast<const void*>(&g_run_tl);
+  const size_t size = which == 0 ? sizeof(g_tl) : which == 1 ? sizeof(g_tl_ep) : sizeof(g_run_tl);
+  if (!reset) {
+    if (!dst || bytes > size) return MPC_ERR_ARG;
+    return hipMemcpyFromSymbol(dst, sym, bytes, 0, hipMemcpyDeviceToHost) == hipSuccess
+               ? MPC_OK
+               : MPC_ERR_HIP;
   }
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_run_tl), sizeof(g_run_tl)) == hipSuccess ? 0 : -1;
+  unsigned long long* rest = static_cast<unsigned long long*>(calloc(size / 8, 8));
+  if (!rest) return MPC_ERR_HIP;
+  if (which == 2)
+    for (size_t j = 0; j < size / 8; j += 8) rest[j + 3] = ~0ull;
+  const hipError_t e = hipMemcpyToSymbol(sym, rest, size, 0, hipMemcpyHostToDevice);
+  free(rest);
+  return e == hipSuccess ? MPC_OK : MPC_ERR_HIP;
 }
 #endif
 
@@ -1420,7 +1438,7 @@ size_t mpc_episodes_state_bytes(int32_t n_robots) {
 
 int mpc_episodes_reset(const mpc_episode_config_t* cfgs, int32_t n_robots, void* state,
                        mpc_stream_t stream) {
-  if (!cfgs || !state || n_robots < 1 || n_robots > 65535) return MPC_ERR_ARG;
+  if (!cfgs || !state || n_robots < 1 || n_robots > kEpMaxRobots) return MPC_ERR_ARG;
   for (int32_t r = 0; r < n_robots; ++r)
     if (check_episode_cfg(&cfgs[r]) != MPC_OK) return MPC_ERR_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -48,30 +48,13 @@
 #include "mpc_exchange.h"
 #include "mpc_finalize.h"
 #include "mpc_lanes.h"
+#include "mpc_timeline.h"
 #include "mpc_winner.h"
 
 namespace mpc {
 
 constexpr int kRunMaxSteps = 64;   // steps per launch (the host splits longer runs)
-
-#ifdef MPC_RUN_STATS
-// Debug builds only (tools/build_variant.sh-style -DMPC_RUN_STATS): 100-MHz
-// stamps per step of the last launch, read by mpc_debug_run_stats:
-//   0 selector step start, 1 records complete, 2 step done (selector),
-//   3 first unit start (min), 4 last loop end (max), 5 last wait end (max),
-//   6 last record stored (max), 7 units that waited
-__device__ unsigned long long g_run_tl[kRunMaxSteps][8];
-#define RUN_T() __builtin_amdgcn_s_memrealtime()
-#define RUN_SET(j, f) (g_run_tl[(j)][(f)] = RUN_T())
-#define RUN_MIN(j, f) atomicMin(&g_run_tl[(j)][(f)], RUN_T())
-#define RUN_MAX(j, f) atomicMax(&g_run_tl[(j)][(f)], RUN_T())
-#define RUN_ADD(j, f) atomicAdd(&g_run_tl[(j)][(f)], 1ull)
-#else
-#define RUN_SET(j, f) ((void)0)
-#define RUN_MIN(j, f) ((void)0)
-#define RUN_MAX(j, f) ((void)0)
-#define RUN_ADD(j, f) ((void)0)
-#endif
+TL_BOUND(kRunSteps, kRunMaxSteps);   // (the RUN_* stamps below: mpc_timeline.h)
 
 // The step's control rows, by value in the kernel arguments.
 struct RunCtl {

@@ -14,6 +14,7 @@
 #include "mpc_argmin.h"
 #include "mpc_device.h"
 #include "mpc_lanes.h"
+#include "mpc_timeline.h"
 
 namespace mpc {
 
@@ -99,6 +100,7 @@ __device__ void emit_winner(const Consts& K, const double* __restrict__ v,
     s_bad = 0;
   }
   __syncthreads();
+  TL_B0(16);
   key = s_key;
   col = s_col;
   const int lane = threadIdx.x;
@@ -128,8 +130,10 @@ __device__ void emit_winner(const Consts& K, const double* __restrict__ v,
       s_c[lane] = rc;
     }
   }
+  TL_B0(17);
   side_a();
   __syncthreads();
+  TL_B0(4);
   // Regular rotation-mode winner: ONE serial pass on lane 0 (heading, rotation,
   // position); every other case keeps the heading chain / sincos phases.
   const bool fast = ROT && s_bad == 0;

@@ -149,24 +149,35 @@ PROTOTYPES = {
 EXPORTS = tuple(PROTOTYPES)
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-# The product build's flags.  The tools that compile the library (tools/resources.py,
-# asm_hazards.py, kernel_digest.py, the timeline builds) take them from here, so a tool
-# cannot analyse another build than the one that ships.
+# The product build's flags.  Every tool that compiles the library does so through
+# compile_cmd() below, so a tool cannot analyse another build than the one that ships.
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ldl",
     # One IEEE rounding per reference operator: no a*b+c contraction.
     "-ffp-contract=off",
     "-Wall",
 ]
+# The timeline variant (csrc/mpc_timeline.h, tools/timeline.py): the stamps compiled in.
+TIMELINE_LIB = os.path.join(REPO_DIR, "tools", "tl_variant.so")
+TIMELINE_DEFINES = ("MPC_TIMELINE",)
 
 
-def build(verbose=False):
-    """Compile csrc/*.hip for gfx950 into the in-tree shared library."""
-    cmd = [HIPCC, *HIPCC_FLAGS, "-I", os.path.join(REPO_DIR, "include"), "-o", LIB_PATH, *SOURCES]
+def compile_cmd(defines=(), out=LIB_PATH, tree=REPO_DIR, extra=()):
+    """The library's compile line, assembled here only.  tree: this repository,
+    or a copy of another revision (SOURCES by name, without those it lacks);
+    extra: a tool's analysis flags."""
+    units = [os.path.join(tree, os.path.relpath(s, REPO_DIR)) for s in SOURCES]
+    return [HIPCC, *HIPCC_FLAGS, *(f"-D{d}" for d in defines), "-I", os.path.join(tree, "include"),
+            *extra, "-o", out, *(u for u in units if tree == REPO_DIR or os.path.exists(u))]
+
+
+def build(verbose=False, defines=(), out=LIB_PATH, tree=REPO_DIR):
+    """Compile csrc/*.hip for gfx950: the in-tree library, or a variant of it."""
+    cmd = compile_cmd(defines, out, tree)
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)
-    return LIB_PATH
+    return out
 
 
 C_HOST_SRC = os.path.join(REPO_DIR, "tests", "c_host", "exchange_episode.cpp")

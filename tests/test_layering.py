@@ -20,13 +20,13 @@ def _includes(path):
             if "/" not in m}
 
 
-def _alone(header, tmp):
+def _alone(header, tmp, *flags):
     tu = os.path.join(tmp, os.path.basename(header)[:-2] + ".hip")
     with open(tu, "w") as fh:
         fh.write(f'#include "{os.path.basename(header)}"\n')
     return subprocess.run([native.HIPCC, "--cuda-host-only", "-fsyntax-only", "-x", "hip",
                            "-std=c++17", "-I", CSRC, "-I", os.path.join(native.REPO_DIR, "include"),
-                           tu], capture_output=True, text=True)
+                           *flags, tu], capture_output=True, text=True)
 
 
 def test_device_headers_stand_alone_and_layered(tmp_path):
@@ -39,6 +39,12 @@ def test_device_headers_stand_alone_and_layered(tmp_path):
     assert _includes(os.path.join(CSRC, "mpc_trig.h")) == set()
     assert _includes(os.path.join(CSRC, "mpc_device.h")) == {"mpc_trig.h"}
     assert _includes(os.path.join(CSRC, "mpc_ftdevice.h")) == {"mpc_device.h"}
+    # the timeline stamps sit below everything: no include at all, and the
+    # header stands alone in its active form too
+    timeline = os.path.join(CSRC, "mpc_timeline.h")
+    assert timeline in HEADERS and "#include" not in open(timeline).read()
+    active = _alone(timeline, str(tmp_path), "-DMPC_TIMELINE")
+    assert active.returncode == 0, active.stderr[-1500:]
     # the episode update is defined (mpc_episode.h) before its callers: no
     # bodiless declaration of it in the headers that used to carry one
     for name in ("mpc_kernels.h", "mpc_finalize.h"):

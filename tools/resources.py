@@ -9,8 +9,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from diplomjourney_amd import native  # noqa: E402
 
-cmd = [native.HIPCC, *native.HIPCC_FLAGS, "-I", os.path.join(REPO, "include"),
-       "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/resources_probe.so", *native.SOURCES]
+cmd = native.compile_cmd(out="/tmp/resources_probe.so",
+                         extra=["-Rpass-analysis=kernel-resource-usage"])
 err = subprocess.run(cmd, capture_output=True, text=True, cwd="/tmp").stderr
 pat = re.compile(sys.argv[1]) if len(sys.argv) > 1 else None
 cur = None
