@@ -7,6 +7,7 @@
 //   step_safe, crit_sqrt, cost      one step and the criterion
 //   Circle .. ObsTable, NoObs, CircleObs   keep-out circles: tables and lane hooks
 //   frame_circle                    a circle in the frame of the rect+cum sums
+//   fleet_d2                        the squared distance a fleet call ranks neighbours by
 //   rollout_candidate_l, rollout_candidate  one candidate as the kernels evaluate it
 //
 // Every function here states one piece of ShittyWizard/DiplomJourney's
@@ -367,6 +368,16 @@ MPC_HD __forceinline__ Circle frame_circle(const Consts& K, const Circle& w, boo
   const double sc = scaled ? K.inv_L : 1.0;
   const double dx = w.cx - K.x, dy = w.cy - K.y;
   return Circle{(K.c0 * dx + K.s0 * dy) * sc, (K.c0 * dy - K.s0 * dx) * sc, w.r2 * (sc * sc), 0.0};
+}
+
+// The squared distance by which a robot of a fleet call ranks another
+// (mpc_episodes_fleet_run, mpc_episodes_fleet.h): q's position minus r's, one
+// fused operation — the form of the circle test above.  Never negative and
+// never -0, so its bits order it.  The fleet model's host build calls this
+// (tests/fleet_harness.cpp).
+MPC_HD __forceinline__ double fleet_d2(double xr, double yr, double xq, double yq) {
+  const double dx = xq - xr, dy = yq - yr;
+  return fma(dy, dy, dx * dx);
 }
 
 // One candidate, exactly as the kernels evaluate it (the host replica in

@@ -30,8 +30,13 @@
 //
 // Keep-out circles (mpc_episodes_run_obstacles) are the same kernel and the
 // same pair rollout with an obstacle hook (Obs; NoObs without circles); the
-// hooks of the modes: mpc_episodes_obs.h.
+// hooks of the modes: mpc_episodes_obs.h.  Robots as each other's circles
+// (mpc_episodes_fleet_run) are the same kernel again, one launch per lockstep
+// step, with a hook whose table each block forms from the other robots'
+// positions: mpc_episodes_fleet.h.
 #pragma once
+
+#include <type_traits>
 
 #include "mpc_argmin.h"
 #include "mpc_device.h"
@@ -53,6 +58,29 @@ struct RobotState {
   int64_t candidates;  // candidates rolled out (the steps' |V| * |B|)
 };
 static_assert(offsetof(RobotState, st) == sizeof(EpisodeHead), "stale trajectory follows the head");
+
+// A hook that declares kFleet forms its table per call from a pose board
+// (FleetObs, mpc_episodes_fleet.h); the others know nothing of it.
+template <class Obs, class = void>
+struct fleet_hook : std::false_type {};
+template <class Obs>
+struct fleet_hook<Obs, std::void_t<decltype(Obs::kFleet)>> : std::true_type {};
+
+// Two kernel arguments made live where this is called: their scalar loads are
+// issued together and waited for once.  A fleet launch's arguments span two
+// cache lines of the kernel-argument segment (the board and the counts behind
+// the 512-B static table; cfgs .. count behind them), and the segment is cold
+// in every scalar cache at every launch: loaded where each is first used, the
+// two lines cost two misses in a row (0.7 us of a launch at 1000 robots;
+// DESIGN.md section 5).
+template <class T>
+__device__ __forceinline__ void kernarg_touch(int a, T* b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" ::"s"(a), "s"(b));
+#else
+  (void)a, (void)b;
+#endif
+}
 
 constexpr int32_t kEpEnded = MPC_EP_ARRIVED | MPC_EP_BREAK | MPC_EP_LIMIT;
 constexpr int32_t kEpMaxRobots = 65535;   // robots of one launch (one block each; the entries refuse more)
@@ -318,6 +346,15 @@ __device__ __forceinline__ int64_t block_sum_i64(int64_t n) {
 // The hook is made by episode_obs(Obs*), found by argument-dependent lookup
 // where the kernel is instantiated: this header, which the host replica's
 // build parses, does not see FrameObs and the chained kernels it pulls in.
+//
+// A fleet call (mpc_episodes_fleet_run; Obs = FleetObs, W = FleetArgs,
+// mpc_episodes_fleet.h) is a launch with max_calls = 1: a running robot's block
+// first forms its table in LDS — the static circles and its chosen neighbours
+// from this call's side of the pose board (obs.select) — and takes the NoObs
+// pair rollout if the table is empty (a uniform branch); every block, stopped
+// or not, writes its robot's position to the board's other side on exit, and
+// count is added to, not written (the entry zeroes it before its launches).
+// Every fleet statement sits under `if constexpr (kFleet)`.
 template <int INTEG, int ROT, class Obs = NoObs, class... W, class... B>
 __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
     W... world, const mpc_episode_config_t* __restrict__ cfgs, RobotState* __restrict__ robots,
@@ -325,6 +362,8 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
     mpc_episodes_progress_t* __restrict__ progress, B* __restrict__... count) {
   static_assert(sizeof...(W) == (Obs::kOn ? 1 : 0) && sizeof...(B) == sizeof...(W),
                 "the table and the count come with a hook, and only with one");
+  constexpr bool kFleet = fleet_hook<Obs>::value;
+  if constexpr (kFleet) kernarg_touch((world, ...).n, (count, ...));   // (both lines, one wait)
   const int r = blockIdx.x;
   const mpc_episode_config_t& c = cfgs[r];
   RobotState* __restrict__ R = &robots[r];
@@ -348,14 +387,20 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
     else
       return Obs{};
   }();
+  if constexpr (kFleet) obs.prefetch((world, ...));   // (the board's first chunk, in flight)
   int64_t cands = 0;                    // (thread 0)
   [[maybe_unused]] int64_t n_blk = 0;   // this lane's blocked candidates
+  [[maybe_unused]] bool fleet_step = false;   // (kFleet) the robot took a step in this launch
   TL_EP_BEGIN();
   for (int call = 0; call < max_calls; ++call) {
     __syncthreads();
     if (s_stop) break;   // uniform
     TL_EP_CALL();
     const EpisodeHead* Hs = reinterpret_cast<const EpisodeHead*>(s_head);
+    if constexpr (kFleet) {   // this call's table (uniform: the whole block is here)
+      obs.select((world, ...), r, Hs->x, Hs->y);
+      fleet_step = true;
+    }
     if (threadIdx.x < 64) {
       int nv, nb;
       episode_grids(c, *Hs, s_v, s_b, nv, nb);
@@ -384,7 +429,19 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       const double bb[2] = {s_b[k0 % nb], s_b[kq % nb]};
       double cst[2];
       [[maybe_unused]] bool blk[2];
-      if (n_steps == 3)   // uniform: the reference's horizon, unrolled
+      if constexpr (kFleet) {
+        if (obs.empty()) {   // uniform: no circle in this call — the loop without circles
+          if (n_steps == 3)
+            const_pair_cost<INTEG, ROT, 3>(K, vv, bb, n_steps, cst);
+          else
+            const_pair_cost<INTEG, ROT, 0>(K, vv, bb, n_steps, cst);
+          blk[0] = blk[1] = false;
+        } else if (n_steps == 3) {
+          const_pair_cost<INTEG, ROT, 3, Obs>(K, vv, bb, n_steps, cst, obs, blk);
+        } else {
+          const_pair_cost<INTEG, ROT, 0, Obs>(K, vv, bb, n_steps, cst, obs, blk);
+        }
+      } else if (n_steps == 3)   // uniform: the reference's horizon, unrolled
         const_pair_cost<INTEG, ROT, 3, Obs>(K, vv, bb, n_steps, cst, obs, blk);
       else
         const_pair_cost<INTEG, ROT, 0, Obs>(K, vv, bb, n_steps, cst, obs, blk);
@@ -503,9 +560,16 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       progress[r].stop = s_stop;
       progress[r].candidates = R->candidates;
     }
-    if constexpr (Obs::kOn) {
+    if constexpr (kFleet) {
+      if (n_blocked) n_blocked[r] += blocked_all;
+      const EpisodeHead* Hs = reinterpret_cast<const EpisodeHead*>(s_head);
+      (world, ...).board_out[r] = {Hs->x, Hs->y};   // where the robot stands after this call
+    } else if constexpr (Obs::kOn) {
       if (n_blocked) n_blocked[r] = blocked_all;
     }
+  }
+  if constexpr (kFleet) {
+    if (!fleet_step) Obs::no_step((world, ...), r);   // uniform
   }
   TL_EP_END();
 }

@@ -1,14 +1,17 @@
 // mpc_episodes_obs.hip — the second translation unit of libmpc_rollout.so: the
 // circle instantiations of the batched robots' episode kernel (k_episodes_run,
-// mpc_episodes.h, with the hooks of mpc_episodes_obs.h) and their launch.  The
-// entry, its checks and the plain instantiations stay in mpc_rollout.hip
-// (episodes_run); why the two are compiled apart: mpc_episodes_obs_launch.h.
+// mpc_episodes.h, with the hooks of mpc_episodes_obs.h) and their launch, and
+// the fleet instantiations of the same kernel (the hook of mpc_episodes_fleet.h),
+// the kernel that fills the pose board, and their launches.  The entries, their
+// checks and the plain instantiations stay in mpc_rollout.hip (episodes_run,
+// episodes_fleet_run); why the two are compiled apart: mpc_episodes_obs_launch.h.
 // (the headers' plain, non-template kernels are mpc_rollout.hip's: one definition
 // per library)
 #define MPC_TEMPLATES_ONLY
 #include "mpc_episodes_obs_launch.h"
 
 #include "mpc_dispatch.h"
+#include "mpc_episodes_fleet.h"
 #include "mpc_episodes_obs.h"
 
 namespace mpc {
@@ -24,5 +27,26 @@ void launch_episodes_run_obs(hipStream_t st, int32_t integrator, const Obstacles
     });
   });
 }
+
+void launch_fleet_begin(hipStream_t st, const RobotState* robots, int n_robots, FleetPos* board) {
+  k_fleet_begin<<<(n_robots + 255) / 256, 256, 0, st>>>(robots, n_robots, board);
+}
+
+void launch_episodes_fleet(hipStream_t st, int32_t integrator, const FleetArgs& A, int n_robots,
+                           const mpc_episode_config_t* cfgs, RobotState* robots, int n_steps,
+                           mpc_episode_log_t* log, int cap, mpc_episodes_progress_t* progress,
+                           int64_t* n_blocked) {
+  dispatch_mode(integrator, [&](auto I, auto R) {
+    k_episodes_run<I, R, FleetObs<R>, FleetArgs><<<n_robots, kBlock, 0, st>>>(
+        A, cfgs, robots, n_steps, 1, log, cap, progress, n_blocked);
+  });
+}
+
+#ifdef MPC_TIMELINE
+const void* fleet_timeline_table(size_t* bytes) {
+  *bytes = sizeof(g_tl_ep);
+  return &g_tl_ep;
+}
+#endif
 
 }  // namespace mpc

@@ -29,6 +29,7 @@
 #include "mpc_episode.h"
 #include "mpc_episode_obs.h"
 #include "mpc_episodes.h"
+#include "mpc_episodes_fleet_launch.h"
 #include "mpc_episodes_obs_launch.h"
 #include "mpc_exchange.h"
 #include "mpc_finalize.h"
@@ -458,15 +459,23 @@ int episode_chain_step(const mpc_episode_config_t* cfg, void* state,
 // the same way: the circles are checked first; with none the plain kernel runs
 // and a count, if asked for, is zeroed on the stream; max_calls == 0 launches
 // nothing and writes nothing.
+// (the checks after the circles': mpc_episodes_fleet_run makes the same, in this order)
+int check_episodes_run(const void* state, int32_t n_robots, int32_t n_steps, int32_t integrator,
+                       int32_t max_calls, const mpc_episode_log_t* log, int32_t log_capacity) {
+  if (!state || n_robots < 1 || n_robots > kEpMaxRobots || n_steps < 1 ||
+      n_steps > MPC_MAX_STEPS || max_calls < 0 || log_capacity < 0 || (log && log_capacity < 1))
+    return MPC_ERR_ARG;
+  return mode_ok(integrator) != MPC_OK ? MPC_ERR_UNSUPPORTED : MPC_OK;
+}
+
 int episodes_run(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
                  int32_t n_robots, int32_t n_steps, int32_t integrator, int32_t max_calls,
                  mpc_episode_log_t* log, int32_t log_capacity, mpc_episodes_progress_t* progress,
                  int64_t* n_blocked_out, mpc_stream_t stream) {
   if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
-  if (!state || n_robots < 1 || n_robots > kEpMaxRobots || n_steps < 1 ||
-      n_steps > MPC_MAX_STEPS || max_calls < 0 || log_capacity < 0 || (log && log_capacity < 1))
-    return MPC_ERR_ARG;
-  if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
+  if (const int bad = check_episodes_run(state, n_robots, n_steps, integrator, max_calls, log,
+                                         log_capacity))
+    return bad;
   if (max_calls == 0) return MPC_OK;
   char* s = static_cast<char*>(state);
   const mpc_episode_config_t* dcfg =
@@ -487,6 +496,45 @@ int episodes_run(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacl
     launch_episodes_run_obs(st, integrator, world_obstacles(obstacles, n_obstacles), n_obstacles,
                             n_robots, dcfg, robots, n_steps, max_calls, log, cap, progress,
                             n_blocked_out);
+  return last_hip_status();
+}
+
+// mpc_episodes_fleet_run: the fleet's own arguments first, then
+// check_episodes_run; the count zeroed on the stream, then one launch per
+// fleet call, launch i on the board's side (call0 + i) & 1; neighbours_out
+// describes the last launch, so only that one gets it.
+int episodes_fleet_run(void* state, void* board, int64_t call0, const mpc_obstacle_t* obstacles,
+                       int32_t n_obstacles, double clearance, double reach, int32_t n_robots,
+                       int32_t n_steps, int32_t integrator, int32_t n_calls,
+                       mpc_episode_log_t* log, int32_t log_capacity,
+                       mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
+                       int32_t* neighbours_out, mpc_stream_t stream) {
+  if (check_obstacles(obstacles, n_obstacles) != MPC_OK || !isfinite(clearance) ||
+      !(clearance > 0) || !isfinite(reach) || reach < 0 || call0 < 0 || n_calls < 0 || !board)
+    return MPC_ERR_ARG;
+  if (const int bad = check_episodes_run(state, n_robots, n_steps, integrator, n_calls, log,
+                                         log_capacity))
+    return bad;
+  if (n_calls == 0) return MPC_OK;
+  char* s = static_cast<char*>(state);
+  const mpc_episode_config_t* dcfg =
+      reinterpret_cast<const mpc_episode_config_t*>(s + episodes_cfg_offset(n_robots));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (n_blocked_out &&
+      hipMemsetAsync(n_blocked_out, 0, static_cast<size_t>(n_robots) * sizeof(*n_blocked_out),
+                     st) != hipSuccess)
+    return MPC_ERR_HIP;
+  FleetPos* side[2] = {static_cast<FleetPos*>(board), static_cast<FleetPos*>(board) + n_robots};
+  FleetArgs A{world_obstacles(obstacles, n_obstacles), nullptr, nullptr, clearance * clearance,
+              reach * reach, n_obstacles, n_robots, nullptr};
+  for (int32_t i = 0; i < n_calls; ++i) {
+    const int at = static_cast<int>((call0 + i) & 1);
+    A.board_in = side[at];
+    A.board_out = side[at ^ 1];
+    A.neighbours = i == n_calls - 1 ? neighbours_out : nullptr;
+    launch_episodes_fleet(st, integrator, A, n_robots, dcfg, reinterpret_cast<RobotState*>(s),
+                          n_steps, log, log ? log_capacity : 0, progress, n_blocked_out);
+  }
   return last_hip_status();
 }
 
@@ -944,16 +992,22 @@ int mpc_episode_chain_step_obstacles(
 #ifdef MPC_TIMELINE
 // Variant builds only (-DMPC_TIMELINE; not in include/mpc_rollout.h: tools/timeline.py
 // binds it): the stamp tables of mpc_timeline.h.  which: 0 the chained step's
-// (g_tl), 1 workload R's (g_tl_ep), 2 the persistent run's (g_run_tl).  reset:
+// (g_tl), 1 workload R's (g_tl_ep), 2 the persistent run's (g_run_tl), 3 the
+// second unit's g_tl_ep (the last fleet call's launch).  reset:
 // the table back to its rest values (zero; the run's min field all ones), dst
 // unused; else its first `bytes` bytes into dst (more than the table: an error).
 int mpc_debug_timeline(int which, void* dst, size_t bytes, int reset) {
-  if (which < 0 || which > 2) return MPC_ERR_ARG;
+  if (which < 0 || which > 3) return MPC_ERR_ARG;
   // (the symbols by address: the runtime's untyped overloads)
-  const void* sym = which == 0 ? static_cast<const void*>(&g_tl)
+  size_t fleet_size = 0;
+  const void* sym = which == 0   ? static_cast<const void*>(&g_tl)
                     : which == 1 ? static_cast<const void*>(&g_tl_ep)
-                                 : static_cast<const void*>(&g_run_tl);
-  const size_t size = which == 0 ? sizeof(g_tl) : which == 1 ? sizeof(g_tl_ep) : sizeof(g_run_tl);
+                    : which == 2 ? static_cast<const void*>(&g_run_tl)
+                                 : fleet_timeline_table(&fleet_size);
+  const size_t size = which == 0   ? sizeof(g_tl)
+                      : which == 1 ? sizeof(g_tl_ep)
+                      : which == 2 ? sizeof(g_run_tl)
+                                   : fleet_size;
   if (!reset) {
     if (!dst || bytes > size) return MPC_ERR_ARG;
     return hipMemcpyFromSymbol(dst, sym, bytes, 0, hipMemcpyDeviceToHost) == hipSuccess
@@ -1467,6 +1521,29 @@ int mpc_episodes_run_obstacles(void* state, const mpc_obstacle_t* obstacles, int
                                mpc_stream_t stream) {
   return episodes_run(state, obstacles, n_obstacles, n_robots, n_steps, integrator, max_calls, log,
                       log_capacity, progress, n_blocked_out, stream);
+}
+
+size_t mpc_episodes_fleet_board_bytes(int32_t n_robots) {
+  return n_robots < 1 ? 0 : fleet_board_bytes(n_robots);
+}
+
+int mpc_episodes_fleet_begin(const void* state, int32_t n_robots, void* board,
+                             mpc_stream_t stream) {
+  if (!state || !board || n_robots < 1 || n_robots > kEpMaxRobots) return MPC_ERR_ARG;
+  launch_fleet_begin(reinterpret_cast<hipStream_t>(stream), static_cast<const RobotState*>(state),
+                     n_robots, static_cast<FleetPos*>(board));
+  return last_hip_status();
+}
+
+int mpc_episodes_fleet_run(void* state, void* board, int64_t call0,
+                           const mpc_obstacle_t* obstacles, int32_t n_obstacles, double clearance,
+                           double reach, int32_t n_robots, int32_t n_steps, int32_t integrator,
+                           int32_t n_calls, mpc_episode_log_t* log, int32_t log_capacity,
+                           mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
+                           int32_t* neighbours_out, mpc_stream_t stream) {
+  return episodes_fleet_run(state, board, call0, obstacles, n_obstacles, clearance, reach,
+                            n_robots, n_steps, integrator, n_calls, log, log_capacity, progress,
+                            n_blocked_out, neighbours_out, stream);
 }
 
 // ----------------------------- full tree -----------------------------------

@@ -14,7 +14,9 @@
 //                                 g_tl_ep[8 * blockIdx.x + q] at the end (6: calls)
 //   RUN_SET / _MIN / _MAX / _ADD(j, f)   persistent run: g_run_tl[j][f]
 // A table is static to its translation unit: the circle instantiations of
-// k_episodes_run (mpc_episodes_obs.hip) stamp a copy that no entry reads.
+// k_episodes_run and its fleet instantiations (mpc_episodes_obs.hip) stamp a
+// copy that mpc_debug_timeline reads as its table 3 (a fleet call is a launch:
+// the last call's phases).
 // Bounds: the tables are sized by the constants that bound the grids (TL_BOUND
 // beside each), and every stamp tests its own index as well: none writes past
 // its table whatever launches the code it sits in.

@@ -75,8 +75,9 @@ class DeviceEpisodes(_RobotBatch):
     They are passed with every run() (mpc_episodes_run_obstacles) and are not
     part of the state.  read_blocked(): per robot the candidates blocked in
     the steps of the last run().  With no circles run() is the call made
-    without the feature.  Not provided: a table per robot, robots as each
-    other's obstacles."""
+    without the feature.  Robots as each other's obstacles: DeviceFleet,
+    below.  Not provided: a table per robot, a radius per robot, a prediction
+    of the others' motion, circles in the full-tree episodes."""
 
     def __init__(self, engine, cfgs, n_steps=3, integrator="qk21", log_capacity=1024,
                  obstacles=()):
@@ -132,6 +133,82 @@ class DeviceEpisodes(_RobotBatch):
         if not self._counted:
             return np.zeros(self.R, dtype=np.int64)
         return self.n_blocked.cpu().numpy().copy()
+
+
+def fleet_reach(cfgs, n_steps, clearance):
+    """The reach beyond which a robot cannot matter to another within one
+    fleet call: max over the cfgs of n_steps * delta_t * max(|v_max|, |v_min|)
+    — the farthest any step-end state of the horizon lies from the start, every
+    layer driven at the velocity bound — times (1 + 2**-40) for the roundings
+    of the step length and the recurrence, plus clearance.  A robot at that
+    distance or beyond has its circle out of every candidate's states."""
+    far = max(int(n_steps) * c.delta_t * max(abs(c.v_max), abs(c.v_min)) for c in cfgs)
+    return far * (1.0 + 2.0 ** -40) + float(clearance)
+
+
+class DeviceFleet(DeviceEpisodes):
+    """DeviceEpisodes whose robots keep clear of each other
+    (mpc_episodes_fleet_begin / _run, csrc/mpc_episodes_fleet.h): a FLEET CALL
+    advances every still-running robot by exactly one MPC step, during which
+    robot r's circles are the static `obstacles` and one circle of radius
+    `clearance` around each chosen other robot, where that robot stood when
+    the call began (ended robots stay where they stand and stay obstacles).
+    Chosen: of the robots nearer than `reach`, the 16 - len(obstacles) nearest,
+    ties to the lower index.  `run(k)` is ONE ABI call for k fleet calls (one
+    launch each: lockstep is the stream's order, nothing waits).
+
+    reach=None: fleet_reach(cfgs, n_steps, clearance), the largest distance a
+    robot of the batch covers in one horizon plus clearance; a larger reach
+    changes nothing, a smaller one ignores robots that could have mattered.
+    The object owns the pose board, the count of fleet calls since reset()
+    and the neighbour buffer.  read_blocked(): per robot the candidates
+    blocked over the fleet calls of the last run().  read_neighbours(): the
+    last fleet call's (within reach before the cap, chosen robots in ascending
+    (distance, index) order) per robot.
+    Not provided: the others' motion over the horizon, per-robot radii,
+    per-robot static tables."""
+
+    def __init__(self, engine, cfgs, clearance, n_steps=3, integrator="qk21", log_capacity=1024,
+                 obstacles=(), reach=None):
+        cfgs = list(cfgs)
+        self.clearance = float(clearance)
+        self.reach = fleet_reach(cfgs, n_steps, clearance) if reach is None else float(reach)
+        n = len(cfgs)
+        self.board = torch.zeros(native.lib().mpc_episodes_fleet_board_bytes(n), dtype=torch.uint8,
+                                 device=engine.device)
+        self.neighbours = torch.full((n, 1 + MPC_MAX_OBSTACLES), -1, dtype=torch.int32,
+                                     device=engine.device)
+        self.neighbours[:, 0] = 0
+        self.call0 = 0
+        super().__init__(engine, cfgs, n_steps, integrator, log_capacity, obstacles)
+
+    def reset(self):
+        super().reset()
+        self._C.mpc_episodes_fleet_begin(self.state.data_ptr(), self.R, self.board.data_ptr(),
+                                         native.current_stream())
+        self.call0 = 0
+        self.neighbours.fill_(-1)        # (read_neighbours(): (0, []) until the next run())
+        self.neighbours[:, 0] = 0
+
+    def run(self, n_calls):
+        """Enqueue n_calls fleet calls: one MPC step of every still-running
+        robot each."""
+        n_calls = int(n_calls)
+        self._C.mpc_episodes_fleet_run(
+            self.state.data_ptr(), self.board.data_ptr(), self.call0, self._obs, self._n_obs,
+            self.clearance, self.reach, self.R, self.n_steps, self._integ, n_calls,
+            self.log.data_ptr(), self.log_capacity, self.progress.data_ptr(),
+            self.n_blocked.data_ptr(), self.neighbours.data_ptr(), native.current_stream())
+        if n_calls > 0:
+            self._counted = True
+            self.call0 += n_calls
+
+    def read_neighbours(self):
+        """Per robot (within, chosen) of the last fleet call (syncs): the robots
+        within reach before the cap, and the chosen ones' indices, nearest
+        first; (0, []) for a robot that took no step in it."""
+        raw = self.neighbours.cpu().numpy()
+        return [(int(row[0]), [int(q) for q in row[1:] if q >= 0]) for row in raw]
 
 
 class DeviceFtEpisodes(_RobotBatch):

@@ -30,7 +30,7 @@ from . import math_model_tree as mmt
 from .abi import (MPC_EP_ARRIVED, MPC_EP_BREAK, MPC_EP_EVENT, MPC_EP_LIMIT, MPC_EP_STALE,
                   MPC_EP_STUCK, make_problem)
 from .device_episode import DeviceEpisode  # noqa: F401
-from .device_episodes import DeviceEpisodes, DeviceFtEpisodes  # noqa: F401
+from .device_episodes import DeviceEpisodes, DeviceFleet, DeviceFtEpisodes  # noqa: F401
 from .distributed import exchange_winner, shard_range
 from .episode_config import (CHAIN_ERRORS, ChainError, reference_episode_config,  # noqa: F401
                              tree_episode_config)

@@ -139,6 +139,12 @@ PROTOTYPES = {
     "mpc_episodes_run": (c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
     "mpc_episodes_run_obstacles": (c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P,
                                            _P]),
+    # the fleet call: (state, board, call0), (circles, count), clearance, reach, then
+    # mpc_episodes_run's arguments from n_robots on, + n_blocked_out and neighbours_out
+    "mpc_episodes_fleet_board_bytes": (c_size_t, [_I32]),
+    "mpc_episodes_fleet_begin": (c_int, [_P, _I32, _P, _P]),
+    "mpc_episodes_fleet_run": (c_int, [_P, _P, _I64, _P, _I32, _D, _D, _I32, _I32, _I32, _I32, _P,
+                                       _I32, _P, _P, _P, _P]),
     "mpc_fulltree_episodes_state_bytes": (c_size_t, [_I32]),
     "mpc_fulltree_episodes_reset": (c_int, [_P, _I32, _P, _P]),
     "mpc_fulltree_episodes_run": (c_int, [_P, _I32, _P, _I32, _P, _I32, _D, _D, _D, _I32, _I32,

@@ -27,7 +27,7 @@ import torch
 from . import config as _cfg
 from .abi import (MPC_EP_ARRIVED, MPC_EP_BREAK, MPC_EP_NO_TRAJ, MpcFulltreeEpisodeConfig,
                   MpcFulltreeProblem)
-from .device_episodes import DeviceEpisodes, DeviceFtEpisodes
+from .device_episodes import DeviceEpisodes, DeviceFleet, DeviceFtEpisodes
 from .episode_config import tree_episode_config
 from .expansion import (Expansion, fulltree_argmin, fulltree_argmin_batched, fulltree_result,
                         fulltree_results)
@@ -426,25 +426,33 @@ def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, sta
     at most 16).  None takes a copy of math_model_tree.barriers at the call,
     the list run_tree_episode's predictive_control scores against, so that
     the batched and the sequential driver agree; a sequence, () included,
-    overrides it.  Not provided: a table per robot, robots as each other's
-    obstacles."""
+    overrides it.  Robots as each other's obstacles: run_tree_fleet.  Not
+    provided: a table per robot, a radius per robot, a prediction of the
+    others' motion, circles in the full tree (run_batched)."""
     eng = engine or _device()[0]
     if obstacles is None:
         from . import math_model_tree as mmt
         obstacles = list(mmt.barriers)
-    R = len(starts)
     if max_calls == 0:
         return [([], "on_target" if is_on_target(s[0], s[1], s[3], s[4]) else "max_calls")
                 for s in starts]
     cap = min(chunk, max_calls) if max_calls else chunk
     eps = DeviceEpisodes(eng, [tree_episode_config(s, max_calls) for s in starts], 3, integrator,
                          log_capacity=cap, obstacles=obstacles)
+    return _drive(eps, cap, bool(len(obstacles)), stats)
+
+
+def _drive(eps, cap, counted, stats):
+    """run(cap) until every robot of the batch has stopped, the log read back
+    once per run: [(records, stop)] and the stats of run_tree_batched.
+    counted: read_blocked() after every run."""
+    R = eps.R
     records = [[] for _ in range(R)]
     found_any = np.zeros(R, dtype=bool)
     blocked = 0
     while True:
         eps.run(cap)
-        if len(obstacles):
+        if counted:
             blocked += int(eps.read_blocked().sum())
         logs = eps.read_logs(first_step=[len(r) for r in records])
         calls, stop, cands = eps.read_progress()
@@ -466,8 +474,36 @@ def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, sta
     return [(records[r], _stop_name(stop[r])) for r in range(R)]
 
 
+def run_tree_fleet(starts, clearance, max_calls=None, integrator="qk21", engine=None, stats=None,
+                   chunk=1024, obstacles=None, reach=None):
+    """run_tree_batched for robots that keep clear of each other
+    (device_episodes.DeviceFleet, mpc_episodes_fleet_run): the episodes advance
+    in lockstep, one MPC step of every still-running robot per fleet call, and
+    during it every other robot nearer than `reach` is a keep-out circle of
+    radius `clearance` where it stood when the call began — beside the static
+    `obstacles` (None: math_model_tree.barriers at the call), and at most 16
+    circles in all, the nearest robots first.  An episode that has ended
+    (on target, stuck, at max_calls) leaves its robot standing as an obstacle.
+    `chunk` fleet calls per host call, the log read back once per host call.
+    reach=None: device_episodes.fleet_reach.  The return value and the stats
+    keys are run_tree_batched's ("blocked" counts the robots' circles too).
+    Not provided: a prediction of the others' motion over the horizon, a
+    radius or a static table per robot, the full tree."""
+    eng = engine or _device()[0]
+    if obstacles is None:
+        from . import math_model_tree as mmt
+        obstacles = list(mmt.barriers)
+    if max_calls == 0:
+        return [([], "on_target" if is_on_target(s[0], s[1], s[3], s[4]) else "max_calls")
+                for s in starts]
+    cap = min(chunk, max_calls) if max_calls else chunk
+    eps = DeviceFleet(eng, [tree_episode_config(s, max_calls) for s in starts], clearance, 3,
+                      integrator, log_capacity=cap, obstacles=obstacles, reach=reach)
+    return _drive(eps, cap, True, stats)
+
+
 __all__ = ["configure", "shard_over", "draw_starts", "run_batched", "run_batched_lockstep",
            "is_on_target",
            "get_distance_from_line", "get_distance_from_target", "saturation", "control_criterion",
            "predictive_control", "start_episode", "run_episode", "prediction_horizon",
-           "run_tree_episode", "run_tree_batched"]
+           "run_tree_episode", "run_tree_batched", "run_tree_fleet"]

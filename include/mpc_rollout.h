@@ -698,7 +698,51 @@ int mpc_episode_chain_error(const void* state, int32_t* error, mpc_stream_t stre
  *                        ran for it, 0 if it ran none (with n_obstacles == 0
  *                        zeroed on `stream`); max_calls == 0 launches nothing
  *                        and leaves it alone, like progress.
- * Not provided: per-robot tables, robots as each other's obstacles.
+ *   mpc_episodes_fleet_begin / _run   the robots keep clear of each other: a
+ *                        FLEET CALL advances every still-running robot by
+ *                        exactly one MPC step (lockstep: one launch per fleet
+ *                        call, ordered by the stream; nothing waits, nothing
+ *                        can hang), and during that step robot r's circles are
+ *                        the n_obstacles static ones, as above, and one circle
+ *                        (x_q, y_q, clearance) for each chosen other robot q:
+ *                        q's position AT THE START OF THIS FLEET CALL, fixed
+ *                        over the horizon.  Ended robots (arrived, stuck, at
+ *                        their limit) stay where they stand and stay obstacles.
+ *                        Chosen: of the robots q != r with d2(r, q) < reach^2 —
+ *                        d2 = fma(dy, dy, dx * dx), (dx, dy) q's position minus
+ *                        r's — the K = MPC_MAX_OBSTACLES - n_obstacles smallest
+ *                        by (d2, q); K = 0: none.  Everything else is
+ *                        mpc_episodes_run_obstacles' (strictly inside, states
+ *                        1..N, all blocked = a stale step, rect+cum in the
+ *                        frame of the step's sums).  A robot with no circle in
+ *                        a call runs the rollout without circles for it.
+ *                        board: device memory of mpc_episodes_fleet_board_bytes
+ *                        (two sides of R positions, 16 B each), owned by the
+ *                        caller.  _begin fills side 0 from the state (after
+ *                        mpc_episodes_reset, on the same stream).  Fleet call c
+ *                        reads side c & 1 and writes the other; call0 is the
+ *                        number of fleet calls made since _begin — the caller
+ *                        keeps it, as it keeps `epoch` for the chained step —
+ *                        and launch i of a _run is fleet call call0 + i.
+ *                        n_calls: fleet calls of this _run (0 launches nothing
+ *                        and writes nothing).
+ *                        n_blocked_out (optional): device int64[R], zeroed on
+ *                        `stream`, then per robot the candidates blocked in
+ *                        the n_calls steps, summed.
+ *                        neighbours_out (optional): device
+ *                        int32[R][1 + MPC_MAX_OBSTACLES], the LAST launch only:
+ *                        [0] the robots within reach before the cap, then the
+ *                        chosen ones in ascending (d2, q) order, then -1; a
+ *                        robot that ran no step in that launch: 0 and -1s.
+ *                        MPC_ERR_ARG before any HIP call: the circle checks of
+ *                        mpc_rollout_partials_obstacles, clearance not finite
+ *                        or <= 0, reach not finite or < 0, call0 < 0, n_calls
+ *                        < 0, board NULL; with valid fleet arguments every
+ *                        other rejection is mpc_episodes_run's, in its order.
+ * Not provided: per-robot static tables, per-robot radii (one clearance for
+ * all), a prediction of the others' motion over the horizon (a neighbour's
+ * circle stands where the neighbour stood when the call began), and the
+ * full-tree episodes (mpc_fulltree_episodes_*), which take no circles at all.
  * ------------------------------------------------------------------------- */
 typedef struct mpc_episodes_progress {
   int32_t calls;         /* MPC steps run so far                                     */
@@ -717,6 +761,15 @@ int mpc_episodes_run_obstacles(void* state, const mpc_obstacle_t* obstacles, int
                                int32_t max_calls, mpc_episode_log_t* log, int32_t log_capacity,
                                mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
                                mpc_stream_t stream);
+size_t mpc_episodes_fleet_board_bytes(int32_t n_robots);
+int mpc_episodes_fleet_begin(const void* state, int32_t n_robots, void* board,
+                             mpc_stream_t stream);
+int mpc_episodes_fleet_run(void* state, void* board, int64_t call0,
+                           const mpc_obstacle_t* obstacles, int32_t n_obstacles, double clearance,
+                           double reach, int32_t n_robots, int32_t n_steps, int32_t integrator,
+                           int32_t n_calls, mpc_episode_log_t* log, int32_t log_capacity,
+                           mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
+                           int32_t* neighbours_out, mpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Full-tree MPC of run_math_model.py / math_model.py.

@@ -7,6 +7,7 @@ against it, on the GPU, and ends with a `JSON ` line.
     python tools/timeline.py chain N_CAND N [soa|tiled|p2p] [--reps 5] [--steps 300]
     python tools/timeline.py episodes [R] [K] [--integ qk21] [--n-steps 3] [--reps 3] [--park I]
     python tools/timeline.py run N_CAND N K [soa|tiled] [--reps 3]
+    python tools/timeline.py fleet [R] [NEIGHBOURS] [--integ qk21] [--reps 5]
 
 chain: the chained step (k_episode_chain), one launch among back-to-back ones
 (tiled: the bench default's tiled batches; p2p: the one-rank P2P exchange form).
@@ -24,6 +25,13 @@ rollout (thread 0's own candidates), argmin (block arg-min + barrier), re-roll
 The plain kernel only: the circle instantiations live in the second translation
 unit and stamp a table of their own that no entry reads.  --park I: robot I
 starts on its target (no call).
+fleet: one fleet call (mpc_episodes_fleet_run, n_calls = 1) beside one
+max_calls = 1 launch of the plain kernel for the same robots (tools/fleet_cost.py's
+clusters: every robot with NEIGHBOURS others within reach, nothing blocked), the
+same phases, the mean over the robots.  The fleet call forms its table — the
+board scan, the selection — between the call's start and the grid's barrier, so
+its `grid` phase less the plain one's is what the selection takes (the second
+unit's table: mpc_debug_timeline's which = 3).
 run: the persistent run (k_episode_run), per step of the last launch (the
 fields: csrc/mpc_timeline.h)."""
 import argparse
@@ -43,7 +51,7 @@ B0_P2P = {1: "candidate", 2: "posted", 3: "gathered", 6: "advance", 8: "publishe
 TILE = ["entry", "DMAs issued", "final consts", "record stored", "costs done", "argmin done"]
 PH = ["grid", "rollout", "argmin", "re-roll", "advance", "log"]
 RUN_STEPS = 64           # tl::kRunSteps
-CHAIN_TL, EPISODES_TL, RUN_TL = 0, 1, 2   # mpc_debug_timeline's `which`
+CHAIN_TL, EPISODES_TL, RUN_TL, FLEET_TL = 0, 1, 2, 3   # mpc_debug_timeline's `which`
 
 
 def variant():
@@ -174,6 +182,48 @@ def episodes(a):
     print("JSON " + json.dumps({"per_call_ns": per, "robots": tl, "state": digest(eps)}))
 
 
+def fleet(a):
+    L = variant()
+    import torch
+    from diplomjourney_amd.device_episodes import DeviceEpisodes, DeviceFleet
+    from diplomjourney_amd.expansion import Expansion
+    from tools import fleet_cost as FC
+    eng = Expansion("cuda:0")
+    R = a.robots
+    cfgs = FC.fleet_configs(R, a.neighbours)
+    batches = {"plain": (EPISODES_TL, DeviceEpisodes(eng, cfgs, 3, a.integ, log_capacity=1)),
+               "fleet": (FLEET_TL, DeviceFleet(eng, cfgs, FC.CLEARANCE, 3, a.integ,
+                                               log_capacity=1, reach=FC.REACH))}
+    out = {}
+    for name, (which, ep) in batches.items():
+        mean = [0.0] * 6
+        for _ in range(a.reps):
+            ep.reset()
+            assert L.mpc_debug_timeline(which, None, 0, 1) == 0
+            torch.cuda.synchronize()
+            ep.run(1)
+            torch.cuda.synchronize()
+            raw = table(L, which, 8 * R)
+            assert all(raw[8 * r + 6] == 1 for r in range(R)), "a robot without its one call"
+            for q in range(6):
+                mean[q] += sum(raw[8 * r + q] for r in range(R)) * 10.0 / (R * a.reps)
+        out[name] = dict(zip(PH, mean))
+        # the last rep's blocks: the launch ends with its slowest
+        tot = sorted(sum(raw[8 * r:8 * r + 6]) * 10 for r in range(R))
+        out[name + "_block_ns_p50_p99_max"] = [tot[len(tot) // 2], tot[(99 * len(tot)) // 100],
+                                               tot[-1]]
+        print(f"{name:5s} " + "  ".join(f"{k} {v:.0f}" for k, v in out[name].items())
+              + f"  total {sum(mean):.0f} ns/call; blocks p50 / p99 / max "
+              + " / ".join(str(t) for t in out[name + "_block_ns_p50_p99_max"]), flush=True)
+    within = [w for w, _ in batches["fleet"][1].read_neighbours()]
+    out["selection_ns"] = out["fleet"]["grid"] - out["plain"]["grid"]
+    out["share_of_call"] = out["selection_ns"] / sum(out["fleet"][k] for k in PH)
+    print(f"selection (grid, fleet less plain): {out['selection_ns']:.0f} ns, "
+          f"{100 * out['share_of_call']:.1f} % of the fleet call's phases; neighbours "
+          f"{min(within)}..{max(within)}")
+    print("JSON " + json.dumps({"robots": R, "neighbours": a.neighbours, "integ": a.integ, **out}))
+
+
 def run_steps(n, ns, K, mode, reps, before=None):
     """reps persistent runs of K steps each (before(rep): ahead of each)."""
     import torch
@@ -209,6 +259,7 @@ MODES = {
     "episodes": (episodes, {"robots": 1000, "calls": 1000},
                  {"integ": "qk21", "n-steps": 3, "reps": 3, "park": None}),
     "run": (run, {"n_cand": None, "n_steps": None, "k": None, "mode": "soa"}, {"reps": 3}),
+    "fleet": (fleet, {"robots": 1000, "neighbours": 4}, {"integ": "qk21", "reps": 5}),
 }
 
 
