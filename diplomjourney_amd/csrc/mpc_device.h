@@ -380,6 +380,17 @@ MPC_HD __forceinline__ double fleet_d2(double xr, double yr, double xq, double y
   return fma(dy, dy, dx * dx);
 }
 
+// One coordinate of a neighbour's circle at horizon step j (1..N: the state
+// after step j) of a predicted fleet call (mpc_episodes_fleet_run_predicted):
+// where the neighbour stood when the call began plus j times its last call's
+// displacement — the product rounded, then the sum (two roundings, never
+// fused).  d = 0 gives x back bit for bit (x + 0.0; a position is never -0
+// where it matters: the circle test takes differences).  The fleet motion
+// model's host build calls this (tests/fleet_motion_harness.cpp).
+MPC_HD __forceinline__ double fleet_predict(double x, double d, int j) {
+  return x + static_cast<double>(j) * d;
+}
+
 // One candidate, exactly as the kernels evaluate it (the host replica in
 // tests/replica_harness.cpp calls this): the core recurrence, and if that
 // flags the candidate, the safe recurrence.  traj (optional) gets the

@@ -65,6 +65,13 @@ template <class Obs, class = void>
 struct fleet_hook : std::false_type {};
 template <class Obs>
 struct fleet_hook<Obs, std::void_t<decltype(Obs::kFleet)>> : std::true_type {};
+// A fleet hook that declares kMotion has one table per horizon step (the
+// neighbours' circles move: FleetMotionObs): it is given the step's index
+// (loop_step, world_step) and publishes the robot's displacement on exit.
+template <class Obs, class = void>
+struct motion_hook : std::false_type {};
+template <class Obs>
+struct motion_hook<Obs, std::void_t<decltype(Obs::kMotion)>> : std::true_type {};
 
 // Two kernel arguments made live where this is called: their scalar loads are
 // issued together and waited for once.  A fleet launch's arguments span two
@@ -139,17 +146,20 @@ __device__ __forceinline__ void const_pair_cost_l(const Consts& K, const double 
     bad[j] = false;
     if constexpr (Obs::kOn) blocked[j] = false;
   }
-  auto one_step = [&]() {
+  auto one_step = [&]([[maybe_unused]] int st) {
 #pragma unroll
     for (int j = 0; j < 2; ++j)
       step_core<INTEG, ROT, PL2>(x[j], y[j], ph[j], s[j], c[j], v[j], b[j], K, bad[j]);
-    if constexpr (Obs::kOn) obs.template loop<2>(x, y, blocked);
+    if constexpr (motion_hook<Obs>::value)
+      obs.template loop_step<2>(st, x, y, blocked);   // (this step's table)
+    else if constexpr (Obs::kOn)
+      obs.template loop<2>(x, y, blocked);
   };
   if constexpr (NS > 0) {
 #pragma unroll
-    for (int st = 0; st < NS; ++st) one_step();
+    for (int st = 0; st < NS; ++st) one_step(st);
   } else {
-    for (int st = 0; st < n_steps; ++st) one_step();
+    for (int st = 0; st < n_steps; ++st) one_step(st);
   }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -163,7 +173,10 @@ __device__ __forceinline__ void const_pair_cost_l(const Consts& K, const double 
       if constexpr (Obs::kOn) blocked[j] = false;   // the recompute's states replace the loop's
       for (int st = 0; st < n_steps; ++st) {
         step_safe<INTEG>(x[j], y[j], ph[j], v[j], b[j], K);
-        if constexpr (Obs::kOn) obs.world(x[j], y[j], blocked[j]);
+        if constexpr (motion_hook<Obs>::value)
+          obs.world_step(st, x[j], y[j], blocked[j]);
+        else if constexpr (Obs::kOn)
+          obs.world(x[j], y[j], blocked[j]);
       }
     }
     cst[j] = cost(x[j], y[j], K);
@@ -355,6 +368,11 @@ __device__ __forceinline__ int64_t block_sum_i64(int64_t n) {
 // or not, writes its robot's position to the board's other side on exit, and
 // count is added to, not written (the entry zeroes it before its launches).
 // Every fleet statement sits under `if constexpr (kFleet)`.
+// A predicted fleet call (mpc_episodes_fleet_run_predicted; Obs = FleetMotionObs,
+// W = FleetMotionArgs) is a fleet call whose table has one part per horizon
+// step: the pair rollout hands the hook the step's index, and the block writes
+// the robot's displacement to the motion board's other side on exit.  Every
+// such statement sits under `if constexpr (kMotion)` (motion_hook).
 template <int INTEG, int ROT, class Obs = NoObs, class... W, class... B>
 __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
     W... world, const mpc_episode_config_t* __restrict__ cfgs, RobotState* __restrict__ robots,
@@ -363,6 +381,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
   static_assert(sizeof...(W) == (Obs::kOn ? 1 : 0) && sizeof...(B) == sizeof...(W),
                 "the table and the count come with a hook, and only with one");
   constexpr bool kFleet = fleet_hook<Obs>::value;
+  constexpr bool kMotion = motion_hook<Obs>::value;
   if constexpr (kFleet) kernarg_touch((world, ...).n, (count, ...));   // (both lines, one wait)
   const int r = blockIdx.x;
   const mpc_episode_config_t& c = cfgs[r];
@@ -391,6 +410,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
   int64_t cands = 0;                    // (thread 0)
   [[maybe_unused]] int64_t n_blk = 0;   // this lane's blocked candidates
   [[maybe_unused]] bool fleet_step = false;   // (kFleet) the robot took a step in this launch
+  [[maybe_unused]] double from_x = 0.0, from_y = 0.0;   // (kMotion) where that step began
   TL_EP_BEGIN();
   for (int call = 0; call < max_calls; ++call) {
     __syncthreads();
@@ -400,6 +420,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
     if constexpr (kFleet) {   // this call's table (uniform: the whole block is here)
       obs.select((world, ...), r, Hs->x, Hs->y);
       fleet_step = true;
+      if constexpr (kMotion) from_x = Hs->x, from_y = Hs->y;
     }
     if (threadIdx.x < 64) {
       int nv, nb;
@@ -564,6 +585,8 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       if (n_blocked) n_blocked[r] += blocked_all;
       const EpisodeHead* Hs = reinterpret_cast<const EpisodeHead*>(s_head);
       (world, ...).board_out[r] = {Hs->x, Hs->y};   // where the robot stands after this call
+      if constexpr (kMotion)   // ... and how far the call moved it, if it goes on
+        Obs::publish((world, ...), r, fleet_step && !s_stop, from_x, from_y, Hs->x, Hs->y);
     } else if constexpr (Obs::kOn) {
       if (n_blocked) n_blocked[r] = blocked_all;
     }

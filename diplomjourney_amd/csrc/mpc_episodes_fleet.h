@@ -28,6 +28,10 @@
 // business: it takes the NoObs pair rollout for that call (empty()).  rect+cum
 // tests in the frame of the step's sums: form() makes the second table with
 // frame_circle, as FrameObs does.
+//
+// FleetMotionObs, below: the hook of a predicted fleet call
+// (mpc_episodes_fleet_run_predicted), the same selection with one table per
+// horizon step, the neighbours' circles moved by their last displacement.
 #pragma once
 
 #include "mpc_episode_obs.h"
@@ -218,6 +222,105 @@ __device__ __forceinline__ FleetObs<ROT> episode_obs(FleetObs<ROT>*) {
   FleetObs<ROT> o;
   o.world_at = lds_addr(S->world);
   o.loop_at = ROT == kRotCum ? lds_addr(S->frame) : o.world_at;
+  return o;
+}
+
+// ---------------------------------------------------------------------------
+// A predicted fleet call (mpc_episodes_fleet_run_predicted): each chosen
+// neighbour's circle moves with the neighbour's last displacement, read from
+// this call's side of the motion board.  The selection is FleetObs' own
+// (positions at the start of the call); after it the block forms ONE TABLE PER
+// HORIZON STEP in LDS — step j's (1..N) holds the static circles unmoved and
+// each neighbour's circle at (fleet_predict(x, dx, j), fleet_predict(y, dy, j))
+// — at a fixed stride of MPC_MAX_OBSTACLES circles, one entry per thread (a
+// second pass when n_steps * groups * 4 > kBlock).  The lanes' test is
+// FleetObs::test with the table's address advanced by the step's stride: the
+// same broadcast operands, nothing more per lane and step.  rect+cum: form()
+// makes every step's table in the frame of the call's sums.
+constexpr uint32_t kFleetStepStride = MPC_MAX_OBSTACLES * sizeof(Circle);
+
+struct FleetStepTable {
+  Circle c[MPC_MAX_STEPS][MPC_MAX_OBSTACLES];
+};
+
+__device__ __forceinline__ FleetStepTable* fleet_step_world() {
+  __shared__ FleetStepTable s_fleet_step_world;
+  return &s_fleet_step_world;
+}
+__device__ __forceinline__ FleetStepTable* fleet_step_frame() {   // (rect+cum only)
+  __shared__ FleetStepTable s_fleet_step_frame;
+  return &s_fleet_step_frame;
+}
+
+template <int ROT>
+struct FleetMotionObs : FleetObs<ROT> {
+  static constexpr bool kMotion = true;   // (the kernel: the step index at the hook, the motion write)
+  int entries = 0;                        // n_steps * groups * 4 (block-uniform)
+
+  // FleetObs::select, then the per-step tables.  Entry e = (j - 1) * g4 + i:
+  // circle i of step j.
+  __device__ __forceinline__ void select(const FleetMotionArgs& A, int r, double x, double y) {
+    FleetObs<ROT>::select(A, r, x, y);
+    if (this->m == 0) {   // uniform: the call runs without circles
+      entries = 0;
+      return;
+    }
+    FleetLds* S = fleet_lds();
+    FleetStepTable* T = fleet_step_world();
+    const int g4 = this->groups() * kFleetGroup, n_static = A.n_static, m = this->m;
+    entries = A.n_steps * g4;
+    for (int e = threadIdx.x; e < entries; e += kBlock) {
+      const int j = e / g4, i = e - j * g4;
+      Circle cq = S->world[i];
+      if (i >= n_static && i < m) {
+        const FleetPos d = A.motion_in[S->idx[i - n_static]];
+        cq.cx = fleet_predict(cq.cx, d.x, j + 1);
+        cq.cy = fleet_predict(cq.cy, d.y, j + 1);
+      }
+      T->c[j][i] = cq;
+    }
+    __syncthreads();
+  }
+
+  __device__ __forceinline__ void form(const Consts& K, bool scaled) {
+    FleetStepTable* T = fleet_step_world();
+    FleetStepTable* F = fleet_step_frame();
+    const int g4 = this->groups() * kFleetGroup;
+    for (int e = threadIdx.x; e < entries; e += kBlock) {
+      const int j = e / g4, i = e - j * g4;
+      F->c[j][i] = frame_circle(K, T->c[j][i], scaled);
+    }
+    __syncthreads();
+  }
+
+  // st: the step's index from 0 (the state after step st + 1).
+  template <int CPL>
+  __device__ __forceinline__ void loop_step(int st, const double (&x)[CPL], const double (&y)[CPL],
+                                            bool (&blocked)[CPL]) const {
+    FleetObs<ROT>::template test<CPL>(this->loop_at + static_cast<uint32_t>(st) * kFleetStepStride,
+                                      this->groups(), x, y, blocked);
+  }
+  __device__ __forceinline__ void world_step(int st, double x, double y, bool& blocked) const {
+    const double xs[1] = {x}, ys[1] = {y};
+    bool bl[1] = {blocked};
+    FleetObs<ROT>::template test<1>(this->world_at + static_cast<uint32_t>(st) * kFleetStepStride,
+                                    this->groups(), xs, ys, bl);
+    blocked = bl[0];
+  }
+
+  // Block r's entry of the motion board's out side (one thread): the step's
+  // displacement of a robot that goes on, zero of one that does not.
+  __device__ __forceinline__ static void publish(const FleetMotionArgs& A, int r, bool moves,
+                                                 double x0, double y0, double x1, double y1) {
+    A.motion_out[r] = moves ? FleetPos{x1 - x0, y1 - y0} : FleetPos{0.0, 0.0};
+  }
+};
+
+template <int ROT>
+__device__ __forceinline__ FleetMotionObs<ROT> episode_obs(FleetMotionObs<ROT>*) {
+  FleetMotionObs<ROT> o;
+  o.world_at = lds_addr(fleet_step_world()->c);
+  o.loop_at = ROT == kRotCum ? lds_addr(fleet_step_frame()->c) : o.world_at;
   return o;
 }
 

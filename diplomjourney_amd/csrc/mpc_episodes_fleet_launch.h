@@ -37,6 +37,17 @@ struct FleetArgs {
   int32_t* neighbours;         // [n][1 + MPC_MAX_OBSTACLES], or NULL
 };
 
+// A predicted fleet launch's arguments (mpc_episodes_fleet_run_predicted): the
+// fleet launch's, first and unchanged — the plain fleet kernels keep their
+// argument segment — then the motion board's sides, entries {dx, dy} with the
+// pose board's layout and parity, and the horizon (select() forms one table
+// per step).
+struct FleetMotionArgs : FleetArgs {
+  const FleetPos* motion_in;   // this call's side: every robot's last displacement
+  FleetPos* motion_out;        // the other side: block r writes entry r on exit
+  int32_t n_steps;             // the horizon N: tables for steps 1..N
+};
+
 // side 0 of the board from the robots' states
 void launch_fleet_begin(hipStream_t st, const RobotState* robots, int n_robots, FleetPos* board);
 
@@ -47,6 +58,12 @@ void launch_episodes_fleet(hipStream_t st, int32_t integrator, const FleetArgs& 
                            const mpc_episode_config_t* cfgs, RobotState* robots, int n_steps,
                            mpc_episode_log_t* log, int cap, mpc_episodes_progress_t* progress,
                            int64_t* n_blocked);
+
+// The same with FleetMotionObs: one PREDICTED fleet call (A.motion_in / _out set).
+void launch_episodes_fleet_predicted(hipStream_t st, int32_t integrator, const FleetMotionArgs& A,
+                                     int n_robots, const mpc_episode_config_t* cfgs,
+                                     RobotState* robots, mpc_episode_log_t* log, int cap,
+                                     mpc_episodes_progress_t* progress, int64_t* n_blocked);
 
 #ifdef MPC_TIMELINE
 // The second unit's copy of workload R's phase table (mpc_timeline.h: a table is

@@ -1,7 +1,8 @@
 // mpc_episodes_obs.hip — the second translation unit of libmpc_rollout.so: the
 // circle instantiations of the batched robots' episode kernel (k_episodes_run,
 // mpc_episodes.h, with the hooks of mpc_episodes_obs.h) and their launch, and
-// the fleet instantiations of the same kernel (the hook of mpc_episodes_fleet.h),
+// the fleet instantiations of the same kernel (the hooks of mpc_episodes_fleet.h:
+// FleetObs, and FleetMotionObs for the predicted fleet call),
 // the kernel that fills the pose board, and their launches.  The entries, their
 // checks and the plain instantiations stay in mpc_rollout.hip (episodes_run,
 // episodes_fleet_run); why the two are compiled apart: mpc_episodes_obs_launch.h.
@@ -39,6 +40,16 @@ void launch_episodes_fleet(hipStream_t st, int32_t integrator, const FleetArgs& 
   dispatch_mode(integrator, [&](auto I, auto R) {
     k_episodes_run<I, R, FleetObs<R>, FleetArgs><<<n_robots, kBlock, 0, st>>>(
         A, cfgs, robots, n_steps, 1, log, cap, progress, n_blocked);
+  });
+}
+
+void launch_episodes_fleet_predicted(hipStream_t st, int32_t integrator, const FleetMotionArgs& A,
+                                     int n_robots, const mpc_episode_config_t* cfgs,
+                                     RobotState* robots, mpc_episode_log_t* log, int cap,
+                                     mpc_episodes_progress_t* progress, int64_t* n_blocked) {
+  dispatch_mode(integrator, [&](auto I, auto R) {
+    k_episodes_run<I, R, FleetMotionObs<R>, FleetMotionArgs><<<n_robots, kBlock, 0, st>>>(
+        A, cfgs, robots, A.n_steps, 1, log, cap, progress, n_blocked);
   });
 }
 

@@ -503,14 +503,19 @@ int episodes_run(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacl
 // check_episodes_run; the count zeroed on the stream, then one launch per
 // fleet call, launch i on the board's side (call0 + i) & 1; neighbours_out
 // describes the last launch, so only that one gets it.
-int episodes_fleet_run(void* state, void* board, int64_t call0, const mpc_obstacle_t* obstacles,
-                       int32_t n_obstacles, double clearance, double reach, int32_t n_robots,
+// predicted (mpc_episodes_fleet_run_predicted): the motion board checked right
+// after the pose board, its side 0 zeroed on the stream before fleet call 0
+// (nobody has moved yet), and FleetMotionObs' launches on both boards' sides.
+int episodes_fleet_run(void* state, void* board, bool predicted, void* motion, int64_t call0,
+                       const mpc_obstacle_t* obstacles, int32_t n_obstacles, double clearance,
+                       double reach, int32_t n_robots,
                        int32_t n_steps, int32_t integrator, int32_t n_calls,
                        mpc_episode_log_t* log, int32_t log_capacity,
                        mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
                        int32_t* neighbours_out, mpc_stream_t stream) {
   if (check_obstacles(obstacles, n_obstacles) != MPC_OK || !isfinite(clearance) ||
-      !(clearance > 0) || !isfinite(reach) || reach < 0 || call0 < 0 || n_calls < 0 || !board)
+      !(clearance > 0) || !isfinite(reach) || reach < 0 || call0 < 0 || n_calls < 0 || !board ||
+      (predicted && !motion))
     return MPC_ERR_ARG;
   if (const int bad = check_episodes_run(state, n_robots, n_steps, integrator, n_calls, log,
                                          log_capacity))
@@ -527,13 +532,25 @@ int episodes_fleet_run(void* state, void* board, int64_t call0, const mpc_obstac
   FleetPos* side[2] = {static_cast<FleetPos*>(board), static_cast<FleetPos*>(board) + n_robots};
   FleetArgs A{world_obstacles(obstacles, n_obstacles), nullptr, nullptr, clearance * clearance,
               reach * reach, n_obstacles, n_robots, nullptr};
+  FleetPos* moved[2] = {static_cast<FleetPos*>(motion),
+                        predicted ? static_cast<FleetPos*>(motion) + n_robots : nullptr};
+  if (predicted && call0 == 0 &&
+      hipMemsetAsync(moved[0], 0, static_cast<size_t>(n_robots) * sizeof(FleetPos), st) !=
+          hipSuccess)
+    return MPC_ERR_HIP;
   for (int32_t i = 0; i < n_calls; ++i) {
     const int at = static_cast<int>((call0 + i) & 1);
     A.board_in = side[at];
     A.board_out = side[at ^ 1];
     A.neighbours = i == n_calls - 1 ? neighbours_out : nullptr;
-    launch_episodes_fleet(st, integrator, A, n_robots, dcfg, reinterpret_cast<RobotState*>(s),
-                          n_steps, log, log ? log_capacity : 0, progress, n_blocked_out);
+    if (predicted)
+      launch_episodes_fleet_predicted(st, integrator, FleetMotionArgs{A, moved[at], moved[at ^ 1],
+                                                                      n_steps},
+                                      n_robots, dcfg, reinterpret_cast<RobotState*>(s), log,
+                                      log ? log_capacity : 0, progress, n_blocked_out);
+    else
+      launch_episodes_fleet(st, integrator, A, n_robots, dcfg, reinterpret_cast<RobotState*>(s),
+                            n_steps, log, log ? log_capacity : 0, progress, n_blocked_out);
   }
   return last_hip_status();
 }
@@ -1541,9 +1558,25 @@ int mpc_episodes_fleet_run(void* state, void* board, int64_t call0,
                            int32_t n_calls, mpc_episode_log_t* log, int32_t log_capacity,
                            mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
                            int32_t* neighbours_out, mpc_stream_t stream) {
-  return episodes_fleet_run(state, board, call0, obstacles, n_obstacles, clearance, reach,
-                            n_robots, n_steps, integrator, n_calls, log, log_capacity, progress,
-                            n_blocked_out, neighbours_out, stream);
+  return episodes_fleet_run(state, board, false, nullptr, call0, obstacles, n_obstacles, clearance,
+                            reach, n_robots, n_steps, integrator, n_calls, log, log_capacity,
+                            progress, n_blocked_out, neighbours_out, stream);
+}
+
+size_t mpc_episodes_fleet_motion_bytes(int32_t n_robots) {
+  return n_robots < 1 ? 0 : fleet_board_bytes(n_robots);
+}
+
+int mpc_episodes_fleet_run_predicted(void* state, void* board, void* motion, int64_t call0,
+                                     const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                                     double clearance, double reach, int32_t n_robots,
+                                     int32_t n_steps, int32_t integrator, int32_t n_calls,
+                                     mpc_episode_log_t* log, int32_t log_capacity,
+                                     mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
+                                     int32_t* neighbours_out, mpc_stream_t stream) {
+  return episodes_fleet_run(state, board, true, motion, call0, obstacles, n_obstacles, clearance,
+                            reach, n_robots, n_steps, integrator, n_calls, log, log_capacity,
+                            progress, n_blocked_out, neighbours_out, stream);
 }
 
 // ----------------------------- full tree -----------------------------------

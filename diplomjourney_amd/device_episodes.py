@@ -76,8 +76,8 @@ class DeviceEpisodes(_RobotBatch):
     part of the state.  read_blocked(): per robot the candidates blocked in
     the steps of the last run().  With no circles run() is the call made
     without the feature.  Robots as each other's obstacles: DeviceFleet,
-    below.  Not provided: a table per robot, a radius per robot, a prediction
-    of the others' motion, circles in the full-tree episodes."""
+    below (predict=True: their circles move with them).  Not provided: a table
+    per robot, a radius per robot, circles in the full-tree episodes."""
 
     def __init__(self, engine, cfgs, n_steps=3, integrator="qk21", log_capacity=1024,
                  obstacles=()):
@@ -135,14 +135,19 @@ class DeviceEpisodes(_RobotBatch):
         return self.n_blocked.cpu().numpy().copy()
 
 
-def fleet_reach(cfgs, n_steps, clearance):
+def fleet_reach(cfgs, n_steps, clearance, predict=False):
     """The reach beyond which a robot cannot matter to another within one
     fleet call: max over the cfgs of n_steps * delta_t * max(|v_max|, |v_min|)
     — the farthest any step-end state of the horizon lies from the start, every
     layer driven at the velocity bound — times (1 + 2**-40) for the roundings
     of the step length and the recurrence, plus clearance.  A robot at that
-    distance or beyond has its circle out of every candidate's states."""
+    distance or beyond has its circle out of every candidate's states.
+    predict=True (DeviceFleet(predict=True)): 2 * far * (1 + 2**-40) +
+    clearance — a neighbour's step-N circle lies up to one horizon's travel
+    from where the neighbour stands."""
     far = max(int(n_steps) * c.delta_t * max(abs(c.v_max), abs(c.v_min)) for c in cfgs)
+    if predict:
+        return 2 * far * (1.0 + 2.0 ** -40) + float(clearance)
     return far * (1.0 + 2.0 ** -40) + float(clearance)
 
 
@@ -157,23 +162,36 @@ class DeviceFleet(DeviceEpisodes):
     ties to the lower index.  `run(k)` is ONE ABI call for k fleet calls (one
     launch each: lockstep is the stream's order, nothing waits).
 
-    reach=None: fleet_reach(cfgs, n_steps, clearance), the largest distance a
-    robot of the batch covers in one horizon plus clearance; a larger reach
+    predict=True (mpc_episodes_fleet_run_predicted): each chosen neighbour's
+    circle moves over the horizon with the neighbour's last displacement — at
+    step j it stands at (x_q + j * dx_q, y_q + j * dy_q), and the state after
+    step j is tested against the step-j circles only.  A robot that has ended,
+    or has not moved yet (fleet call 0), stands still.  The object then owns
+    the motion board too (two sides of R {dx, dy}, the pose board's parity).
+
+    reach=None: fleet_reach(cfgs, n_steps, clearance, predict), the largest
+    distance a robot of the batch covers in one horizon (predict: two
+    horizons, the neighbour's travel too) plus clearance; a larger reach
     changes nothing, a smaller one ignores robots that could have mattered.
     The object owns the pose board, the count of fleet calls since reset()
     and the neighbour buffer.  read_blocked(): per robot the candidates
     blocked over the fleet calls of the last run().  read_neighbours(): the
     last fleet call's (within reach before the cap, chosen robots in ascending
     (distance, index) order) per robot.
-    Not provided: the others' motion over the horizon, per-robot radii,
-    per-robot static tables."""
+    Not provided: any prediction but the constant displacement, per-robot
+    radii, per-robot static tables."""
 
     def __init__(self, engine, cfgs, clearance, n_steps=3, integrator="qk21", log_capacity=1024,
-                 obstacles=(), reach=None):
+                 obstacles=(), reach=None, predict=False):
         cfgs = list(cfgs)
         self.clearance = float(clearance)
-        self.reach = fleet_reach(cfgs, n_steps, clearance) if reach is None else float(reach)
+        self.predict = bool(predict)
+        self.reach = (fleet_reach(cfgs, n_steps, clearance, self.predict) if reach is None
+                      else float(reach))
         n = len(cfgs)
+        self.motion = (torch.zeros(native.lib().mpc_episodes_fleet_motion_bytes(n),
+                                   dtype=torch.uint8, device=engine.device)
+                       if self.predict else None)
         self.board = torch.zeros(native.lib().mpc_episodes_fleet_board_bytes(n), dtype=torch.uint8,
                                  device=engine.device)
         self.neighbours = torch.full((n, 1 + MPC_MAX_OBSTACLES), -1, dtype=torch.int32,
@@ -194,11 +212,15 @@ class DeviceFleet(DeviceEpisodes):
         """Enqueue n_calls fleet calls: one MPC step of every still-running
         robot each."""
         n_calls = int(n_calls)
-        self._C.mpc_episodes_fleet_run(
-            self.state.data_ptr(), self.board.data_ptr(), self.call0, self._obs, self._n_obs,
-            self.clearance, self.reach, self.R, self.n_steps, self._integ, n_calls,
-            self.log.data_ptr(), self.log_capacity, self.progress.data_ptr(),
-            self.n_blocked.data_ptr(), self.neighbours.data_ptr(), native.current_stream())
+        rest = (self.call0, self._obs, self._n_obs, self.clearance, self.reach, self.R,
+                self.n_steps, self._integ, n_calls, self.log.data_ptr(), self.log_capacity,
+                self.progress.data_ptr(), self.n_blocked.data_ptr(), self.neighbours.data_ptr(),
+                native.current_stream())
+        if self.predict:
+            self._C.mpc_episodes_fleet_run_predicted(self.state.data_ptr(), self.board.data_ptr(),
+                                                     self.motion.data_ptr(), *rest)
+        else:
+            self._C.mpc_episodes_fleet_run(self.state.data_ptr(), self.board.data_ptr(), *rest)
         if n_calls > 0:
             self._counted = True
             self.call0 += n_calls

@@ -427,8 +427,8 @@ def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, sta
     the list run_tree_episode's predictive_control scores against, so that
     the batched and the sequential driver agree; a sequence, () included,
     overrides it.  Robots as each other's obstacles: run_tree_fleet.  Not
-    provided: a table per robot, a radius per robot, a prediction of the
-    others' motion, circles in the full tree (run_batched)."""
+    provided: a table per robot, a radius per robot, circles in the full tree
+    (run_batched)."""
     eng = engine or _device()[0]
     if obstacles is None:
         from . import math_model_tree as mmt
@@ -475,7 +475,7 @@ def _drive(eps, cap, counted, stats):
 
 
 def run_tree_fleet(starts, clearance, max_calls=None, integrator="qk21", engine=None, stats=None,
-                   chunk=1024, obstacles=None, reach=None):
+                   chunk=1024, obstacles=None, reach=None, predict=False):
     """run_tree_batched for robots that keep clear of each other
     (device_episodes.DeviceFleet, mpc_episodes_fleet_run): the episodes advance
     in lockstep, one MPC step of every still-running robot per fleet call, and
@@ -485,10 +485,12 @@ def run_tree_fleet(starts, clearance, max_calls=None, integrator="qk21", engine=
     circles in all, the nearest robots first.  An episode that has ended
     (on target, stuck, at max_calls) leaves its robot standing as an obstacle.
     `chunk` fleet calls per host call, the log read back once per host call.
+    predict=True (mpc_episodes_fleet_run_predicted): a neighbour's circle
+    moves over the horizon with the neighbour's last displacement.
     reach=None: device_episodes.fleet_reach.  The return value and the stats
     keys are run_tree_batched's ("blocked" counts the robots' circles too).
-    Not provided: a prediction of the others' motion over the horizon, a
-    radius or a static table per robot, the full tree."""
+    Not provided: any prediction but the constant displacement, a radius or a
+    static table per robot, the full tree."""
     eng = engine or _device()[0]
     if obstacles is None:
         from . import math_model_tree as mmt
@@ -498,7 +500,8 @@ def run_tree_fleet(starts, clearance, max_calls=None, integrator="qk21", engine=
                 for s in starts]
     cap = min(chunk, max_calls) if max_calls else chunk
     eps = DeviceFleet(eng, [tree_episode_config(s, max_calls) for s in starts], clearance, 3,
-                      integrator, log_capacity=cap, obstacles=obstacles, reach=reach)
+                      integrator, log_capacity=cap, obstacles=obstacles, reach=reach,
+                      predict=predict)
     return _drive(eps, cap, True, stats)
 
 

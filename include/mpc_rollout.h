@@ -739,10 +739,52 @@ int mpc_episode_chain_error(const void* state, int32_t* error, mpc_stream_t stre
  *                        or <= 0, reach not finite or < 0, call0 < 0, n_calls
  *                        < 0, board NULL; with valid fleet arguments every
  *                        other rejection is mpc_episodes_run's, in its order.
+ *   mpc_episodes_fleet_run_predicted   a PREDICTED FLEET CALL: a fleet call in
+ *                        which each chosen neighbour's circle moves with the
+ *                        neighbour's last displacement (a constant-velocity
+ *                        prediction).  Robot r's circles at horizon step j
+ *                        (j = 1..N: the state after step j) are the static
+ *                        ones, unmoved, and for each chosen neighbour q
+ *                        (x_q + j * dx_q, y_q + j * dy_q, clearance), each
+ *                        coordinate computed as x + (double)j * dx (the
+ *                        product rounded, then the sum); (x_q, y_q) and
+ *                        (dx_q, dy_q) are this call's in sides of the two
+ *                        boards.  The state after step j is tested against the
+ *                        step-j circles only (a flagged candidate's recomputed
+ *                        states likewise; rect+cum in the frame of the step's
+ *                        sums).  The selection (by the positions at the start
+ *                        of the call), reach, the cap, neighbours_out,
+ *                        n_blocked_out, the blocked / stale / NaN semantics
+ *                        and the lockstep by stream order are
+ *                        mpc_episodes_fleet_run's.
+ *                        motion: device memory of
+ *                        mpc_episodes_fleet_motion_bytes (two sides of R
+ *                        entries {double dx, dy}, 16 B each, with the pose
+ *                        board's parity: call c reads side c & 1 and writes
+ *                        the other), owned by the caller.  Every block writes
+ *                        its robot's entry of the out side: a robot still
+ *                        running after the call (x_after - x_before,
+ *                        y_after - y_before), one subtraction each, x_before
+ *                        its entry of the pose board's in side; (0.0, 0.0) for
+ *                        a robot that ended in this call, had ended before it
+ *                        or took no step.  With call0 == 0 the entry zeroes
+ *                        side 0 of the motion board on `stream` before its
+ *                        first launch (nobody has moved yet), so fleet call 0
+ *                        of a predicted run is mpc_episodes_fleet_run's, bit
+ *                        for bit.  The pose board, its layout and _begin are
+ *                        unchanged.  The motion board is valid only for an
+ *                        unbroken sequence of predicted calls since call0 = 0:
+ *                        mixing _run and _run_predicted on one board is not
+ *                        supported and not checked.
+ *                        MPC_ERR_ARG before any HIP call: motion NULL (checked
+ *                        right after board); every other rejection is
+ *                        mpc_episodes_fleet_run's, in its order.  n_calls == 0
+ *                        launches nothing and writes nothing (the motion board
+ *                        is not zeroed either).
  * Not provided: per-robot static tables, per-robot radii (one clearance for
- * all), a prediction of the others' motion over the horizon (a neighbour's
- * circle stands where the neighbour stood when the call began), and the
- * full-tree episodes (mpc_fulltree_episodes_*), which take no circles at all.
+ * all), any prediction of the others' motion but the constant displacement of
+ * _run_predicted, and the full-tree episodes (mpc_fulltree_episodes_*), which
+ * take no circles at all.
  * ------------------------------------------------------------------------- */
 typedef struct mpc_episodes_progress {
   int32_t calls;         /* MPC steps run so far                                     */
@@ -770,6 +812,14 @@ int mpc_episodes_fleet_run(void* state, void* board, int64_t call0,
                            int32_t n_calls, mpc_episode_log_t* log, int32_t log_capacity,
                            mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
                            int32_t* neighbours_out, mpc_stream_t stream);
+size_t mpc_episodes_fleet_motion_bytes(int32_t n_robots);
+int mpc_episodes_fleet_run_predicted(void* state, void* board, void* motion, int64_t call0,
+                                     const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                                     double clearance, double reach, int32_t n_robots,
+                                     int32_t n_steps, int32_t integrator, int32_t n_calls,
+                                     mpc_episode_log_t* log, int32_t log_capacity,
+                                     mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
+                                     int32_t* neighbours_out, mpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Full-tree MPC of run_math_model.py / math_model.py.

@@ -24,6 +24,16 @@ a process of its own) stamps the selection per block, and a launch pays it
 once per round of blocks (two blocks per CU at a time).  512 robots are
 measured as well.
 
+The predicted column (mpc_episodes_fleet_run_predicted): predicted_K is one
+predicted fleet call for fleet_K's robots, alternated with it in the same
+process, so predicted_K - fleet_K is what the prediction adds — the motion
+loads, the per-step tables' formation and the motion write.  It is launched as
+fleet call 2 (an even call on a motion board of zeros), so that the row holds
+the launch alone; predicted_4_call0 is fleet call 0, with the entry's
+hipMemsetAsync of the motion board's side 0 inside the event pair.  The
+formation's time per block comes from the stamps as the selection's does
+(tools/timeline.py fleet: formation_ns).
+
     python tools/fleet_cost.py [--launches 40] [--out profiles/fleet/cost.json]
 Needs a GPU (no fallback)."""
 import argparse
@@ -80,12 +90,24 @@ def classes():
                 self.neighbours.data_ptr() if self.counted else None, native.current_stream())
             self.call0 += int(n_calls)
 
-    return Baseline, Fleet
+    class Predicted(Fleet):
+        call = 2        # the fleet call each launch is made as (0: the entry zeroes side 0 first)
+
+        def run(self, n_calls):
+            self._C.mpc_episodes_fleet_run_predicted(
+                self.state.data_ptr(), self.board.data_ptr(), self.motion.data_ptr(), self.call,
+                self._obs, self._n_obs, self.clearance, self.reach, self.R, self.n_steps,
+                self._integ, int(n_calls), self.log.data_ptr(), self.log_capacity,
+                self.progress.data_ptr(), self.n_blocked.data_ptr() if self.counted else None,
+                self.neighbours.data_ptr() if self.counted else None, native.current_stream())
+            self.call0 += int(n_calls)
+
+    return Baseline, Fleet, Predicted
 
 
 def measure(eng, integ, n, launches, warmup):
     import torch
-    Baseline, Fleet = classes()
+    Baseline, Fleet, Predicted = classes()
     far = lambda k: cost_timing.circles(k, lambda i: (-100.0 - 0.1 * i, -100.0))
     objs, variants = {}, [("plain_a", None)]
     objs["plain_a"] = Baseline(eng, fleet_configs(n, 0), 3, integ, log_capacity=1)
@@ -94,12 +116,17 @@ def measure(eng, integ, n, launches, warmup):
         objs[f"obstacles_{k}"] = Baseline(eng, cfgs, 3, integ, log_capacity=1, obstacles=far(k))
         objs[f"obstacles_{k}"].obstacle_entry = True
         objs[f"fleet_{k}"] = Fleet(eng, cfgs, CLEARANCE, 3, integ, log_capacity=1, reach=REACH)
-        variants += [(f"obstacles_{k}", k), (f"fleet_{k}", k)]
+        objs[f"predicted_{k}"] = Predicted(eng, cfgs, CLEARANCE, 3, integ, log_capacity=1,
+                                           reach=REACH, predict=True)
+        variants += [(f"obstacles_{k}", k), (f"fleet_{k}", k), (f"predicted_{k}", k)]
     objs["fleet_4_counted"] = Fleet(eng, fleet_configs(n, 4), CLEARANCE, 3, integ, log_capacity=1,
                                     reach=REACH)
     objs["fleet_4_counted"].counted = True
+    objs["predicted_4_call0"] = Predicted(eng, fleet_configs(n, 4), CLEARANCE, 3, integ,
+                                          log_capacity=1, reach=REACH, predict=True)
+    objs["predicted_4_call0"].call = 0
     objs["plain_b"] = Baseline(eng, fleet_configs(n, 0), 3, integ, log_capacity=1)
-    variants += [("fleet_4_counted", 4), ("plain_b", None)]
+    variants += [("fleet_4_counted", 4), ("predicted_4_call0", 4), ("plain_b", None)]
     variants = tuple(variants)
 
     # ~60 us of device work ahead of every timed launch: the host has enqueued the
@@ -138,6 +165,10 @@ def measure(eng, integ, n, launches, warmup):
         f, o = rows[f"fleet_{k}"], rows[f"obstacles_{k}"]
         f["over_same_circles_us"] = f["median_us"] - o["median_us"]
         f["share_of_call"] = f["over_same_circles_us"] / f["median_us"]
+        p = rows[f"predicted_{k}"]
+        p["over_fleet_us"] = p["median_us"] - f["median_us"]
+        p["over_fleet_share"] = p["over_fleet_us"] / f["median_us"]
+        p["fleet_quartile_band_us"] = [f["p25_us"], f["p75_us"]]
     return {"integrator": integ, "robots": n, "n_steps": 3, "rows": rows,
             "same_step_in_every_row": same, "plain_median_us": base,
             "plain_quartile_band_us": [min(a["p25_us"], b["p25_us"]),
@@ -145,16 +176,16 @@ def measure(eng, integ, n, launches, warmup):
             "fleet_0_over_plain_us": rows["fleet_0"]["median_us"] - base}
 
 
-def stamped_selection_ns(n, integ):
-    """The selection's time per block with nobody in reach, from the stamps:
-    tools/timeline.py fleet N 0 in a process of its own (it loads the variant
-    library), its JSON line's selection_ns."""
+def stamped_ns(n, integ, k=0):
+    """The selection's time per block and the per-step tables' formation, from
+    the stamps: tools/timeline.py fleet N K in a process of its own (it loads
+    the variant library), its JSON line's selection_ns and formation_ns."""
     import subprocess
     out = subprocess.run([sys.executable, os.path.join(REPO, "tools", "timeline.py"), "fleet",
-                          str(n), "0", "--integ", integ], capture_output=True, text=True,
+                          str(n), str(k), "--integ", integ], capture_output=True, text=True,
                          check=True).stdout
-    line = [ln for ln in out.splitlines() if ln.startswith("JSON ")][-1]
-    return float(json.loads(line[5:])["selection_ns"])
+    line = json.loads([ln for ln in out.splitlines() if ln.startswith("JSON ")][-1][5:])
+    return float(line["selection_ns"]), float(line["formation_ns"])
 
 
 def main():
@@ -178,9 +209,14 @@ def main():
             # the scan, measured where it runs: the selection's time per block from
             # the stamps (tools/timeline.py fleet, the variant library, a process of
             # its own), once per round of blocks (two blocks per CU at a time)
-            m["selection_ns_per_block"] = stamped_selection_ns(n, integ)
+            m["selection_ns_per_block"], m["formation_0_ns_per_block"] = stamped_ns(n, integ)
+            m["formation_13_ns_per_block"] = stamped_ns(n, integ, 13)[1]
             m["rounds_of_blocks"] = -(-n // (2 * cus))
             m["scan_us"] = m["selection_ns_per_block"] * m["rounds_of_blocks"] / 1e3
+            m["formation_0_us"] = m["formation_0_ns_per_block"] * m["rounds_of_blocks"] / 1e3
+            f0, p0 = m["rows"]["fleet_0"], m["rows"]["predicted_0"]
+            m["predicted_0_inside_fleet_band_plus_formation"] = (
+                p0["median_us"] <= f0["p75_us"] + max(m["formation_0_us"], 0.0))
             lo, hi = m["plain_quartile_band_us"]
             z = m["rows"]["fleet_0"]["median_us"]
             m["zero_inside_band_plus_scan"] = lo + m["scan_us"] <= z <= hi + m["scan_us"]
@@ -197,11 +233,16 @@ def main():
         print(m["integrator"], m["robots"], "robots: plain band", m["plain_quartile_band_us"],
               "scan", m["scan_us"], "fleet_0 - plain", m["fleet_0_over_plain_us"],
               "zero inside band + scan", m["zero_inside_band_plus_scan"], "same step",
-              m["same_step_in_every_row"])
+              m["same_step_in_every_row"], "formation per block (0 / 13 neighbours, ns)",
+              m["formation_0_ns_per_block"], m["formation_13_ns_per_block"],
+              "predicted_0 inside the fleet band + formation",
+              m["predicted_0_inside_fleet_band_plus_formation"])
         for name, r in m["rows"].items():
             extra = (f"  over same circles {r['over_same_circles_us']:7.2f} us "
                      f"({100 * r['share_of_call']:.1f} % of the call)  neighbours "
-                     f"{r['neighbours_min_max']}" if "share_of_call" in r else "")
+                     f"{r['neighbours_min_max']}" if "share_of_call" in r else
+                     f"  over the fleet call {r['over_fleet_us']:7.2f} us "
+                     f"({100 * r['over_fleet_share']:.1f} %)" if "over_fleet_us" in r else "")
             print(f"  {name:16s} median {r['median_us']:8.2f} us  p25 {r['p25_us']:8.2f}  "
                   f"p75 {r['p75_us']:8.2f}{extra}")
 

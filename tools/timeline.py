@@ -31,7 +31,10 @@ clusters: every robot with NEIGHBOURS others within reach, nothing blocked), the
 same phases, the mean over the robots.  The fleet call forms its table — the
 board scan, the selection — between the call's start and the grid's barrier, so
 its `grid` phase less the plain one's is what the selection takes (the second
-unit's table: mpc_debug_timeline's which = 3).
+unit's table: mpc_debug_timeline's which = 3).  A predicted fleet call
+(mpc_episodes_fleet_run_predicted, fleet call 0: every motion entry zero, the
+work the same) is stamped beside it: its `grid` phase less the fleet call's is
+the per-step tables' formation; the motion write follows the last stamp.
 run: the persistent run (k_episode_run), per step of the last launch (the
 fields: csrc/mpc_timeline.h)."""
 import argparse
@@ -193,7 +196,9 @@ def fleet(a):
     cfgs = FC.fleet_configs(R, a.neighbours)
     batches = {"plain": (EPISODES_TL, DeviceEpisodes(eng, cfgs, 3, a.integ, log_capacity=1)),
                "fleet": (FLEET_TL, DeviceFleet(eng, cfgs, FC.CLEARANCE, 3, a.integ,
-                                               log_capacity=1, reach=FC.REACH))}
+                                               log_capacity=1, reach=FC.REACH)),
+               "predicted": (FLEET_TL, DeviceFleet(eng, cfgs, FC.CLEARANCE, 3, a.integ,
+                                                   log_capacity=1, reach=FC.REACH, predict=True))}
     out = {}
     for name, (which, ep) in batches.items():
         mean = [0.0] * 6
@@ -221,6 +226,12 @@ def fleet(a):
     print(f"selection (grid, fleet less plain): {out['selection_ns']:.0f} ns, "
           f"{100 * out['share_of_call']:.1f} % of the fleet call's phases; neighbours "
           f"{min(within)}..{max(within)}")
+    # a predicted call forms its per-step tables right after the selection (and,
+    # rect+cum, their frame form after the grid's barrier: the rollout phase's head)
+    out["formation_ns"] = out["predicted"]["grid"] - out["fleet"]["grid"]
+    out["predicted_less_fleet_ns"] = {k: out["predicted"][k] - out["fleet"][k] for k in PH}
+    print("predicted less fleet, per phase: "
+          + "  ".join(f"{k} {v:.0f}" for k, v in out["predicted_less_fleet_ns"].items()))
     print("JSON " + json.dumps({"robots": R, "neighbours": a.neighbours, "integ": a.integ, **out}))
 
 
