@@ -385,8 +385,8 @@ MPC_HD __forceinline__ double fleet_d2(double xr, double yr, double xq, double y
 // where the neighbour stood when the call began plus j times its last call's
 // displacement — the product rounded, then the sum (two roundings, never
 // fused).  d = 0 gives x back bit for bit (x + 0.0; a position is never -0
-// where it matters: the circle test takes differences).  The fleet motion
-// model's host build calls this (tests/fleet_motion_harness.cpp).
+// where it matters: the circle test takes differences).  The fleet model's
+// host build calls this too (tests/fleet_harness.cpp).
 MPC_HD __forceinline__ double fleet_predict(double x, double d, int j) {
   return x + static_cast<double>(j) * d;
 }

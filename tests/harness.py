@@ -1,4 +1,5 @@
-"""Builds and loads the host test harnesses (trig_harness.cpp, replica_harness.cpp)."""
+"""Builds and loads the host test harnesses (trig_harness.cpp with g++; every
+other tests/*_harness.cpp as the host side of a HIP translation unit)."""
 import contextlib
 import ctypes
 import glob
@@ -29,6 +30,14 @@ def _build(name, cmd):
     return ctypes.CDLL(out)
 
 
+def host_lib(name):
+    """tests/<name>.cpp as the library's host build: hipcc's host side alone,
+    with the library's -ffp-contract=off."""
+    return _build(name, ["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC",
+                         "-shared", "--cuda-host-only", "-x", "hip", "-I",
+                         os.path.join(REPO, "include")])
+
+
 def trig_lib():
     L = _build("trig_harness", ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC",
                                 "-shared"])
@@ -55,9 +64,7 @@ def tan_small(x):
 
 def replica_lib():
     from diplomjourney_amd.abi import MpcFulltreeProblem, MpcProblem
-    L = _build("replica_harness", ["/opt/rocm/bin/hipcc", "-O2", "-std=c++17",
-                                   "-ffp-contract=off", "-fPIC", "-shared", "--cuda-host-only",
-                                   "-x", "hip", "-I", os.path.join(REPO, "include")])
+    L = host_lib("replica_harness")
     L.replica_rollout.argtypes = [ctypes.POINTER(MpcProblem), _P, _P, ctypes.c_int64,
                                   ctypes.c_int32, ctypes.c_int32, _P, _P]
     L.replica_rollout_device_consts.argtypes = L.replica_rollout.argtypes

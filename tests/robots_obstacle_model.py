@@ -34,7 +34,8 @@ class ObstacleRobotModel(RM.RobotModel):
         """The blocked candidates' costs +inf (RobotModel.mpc_step calls this
         between the rollout and the winner, before the pose moves)."""
         n_grid = len(costs)
-        self.poses.append((self.x, self.y))
+        mask = early = np.zeros(0, dtype=bool)
+        margin = math.inf
         if n_grid:
             mask, margin = ranking.blocked(states, self.circles)
             early = (ranking.blocked(states[:-1], self.circles)[0] if self.n_steps > 1
@@ -43,10 +44,16 @@ class ObstacleRobotModel(RM.RobotModel):
                 none, far = ranking.blocked(states, self.fillers)
                 assert not none.any(), "a filler circle blocks a candidate"
                 margin = min(margin, far)
-            if margin == margin:                  # (NaN: no finite state at all)
-                self.margin = min(self.margin, margin)
-        else:
-            mask = early = np.zeros(0, dtype=bool)
+        return self.scored(states, costs, v, b, mask, early, margin)
+
+    def scored(self, states, costs, v, b, mask, early, margin):
+        """The bookkeeping of a scored step, whatever formed its masks (`mask`:
+        the blocked candidates, `early`: those blocked before the last state
+        alone, `margin`: the step's smallest |distance - r|); the blocked
+        candidates' costs +inf."""
+        self.poses.append((self.x, self.y))
+        if margin == margin:                      # (NaN: no finite state at all)
+            self.margin = min(self.margin, margin)
         self.free.append(RM.winner(states, costs, v, b).index)
         self.masks.append((mask, early))
         self.blocked_steps.append(int(mask.sum()))

@@ -5,7 +5,6 @@ and the preconditions of the GPU cases (tests/test_episode_obstacles_gpu.py)
 on the IEEE replica."""
 import ctypes
 import math
-import os
 
 import numpy as np
 import pytest
@@ -131,10 +130,7 @@ def test_base_rejections_match_the_base_entries_without_gpu():
 # the frame function on the host
 # ----------------------------------------------------------------------------
 def _frame_lib():
-    L = harness._build("frame_harness", ["/opt/rocm/bin/hipcc", "-O2", "-std=c++17",
-                                         "-ffp-contract=off", "-fPIC", "-shared",
-                                         "--cuda-host-only", "-x", "hip", "-I",
-                                         os.path.join(harness.REPO, "include")])
+    L = harness.host_lib("frame_harness")
     L.frame_consts.argtypes = [ctypes.POINTER(abi.MpcProblem), _P]
     L.frame_circles.argtypes = [ctypes.POINTER(abi.MpcProblem), _P, ctypes.c_int, _P]
     L.frame_cum_pose.argtypes = [ctypes.POINTER(abi.MpcProblem), _P, ctypes.c_int, _P]

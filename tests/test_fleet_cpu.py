@@ -2,7 +2,6 @@
 entries reject before any HIP call, the board's size, the model's neighbour
 selection (tests/fleet_model.py) against an independent sort on exact
 arithmetic, and DeviceFleet's default reach against its formula."""
-import ctypes
 import math
 import random
 from fractions import Fraction
@@ -13,19 +12,7 @@ import fleet_model as FM
 import robots_cases as RC
 from diplomjourney_amd import abi, native
 from diplomjourney_amd.device_episodes import fleet_reach
-
-
-def _circles(*rows):
-    return abi.make_obstacles(rows)[0]
-
-
-FAKE = ctypes.c_void_p(0x1000)
-
-
-def _run(L, obs=None, n=0, state=FAKE, board=FAKE, call0=0, clearance=0.1, reach=0.3, n_robots=1,
-         n_steps=3, integ=0, n_calls=1, log=None, cap=0):
-    return L.mpc_episodes_fleet_run(state, board, call0, obs, n, clearance, reach, n_robots,
-                                    n_steps, integ, n_calls, log, cap, None, None, None, None)
+from fleet_cases import FAKE, LATTICE as lattice, circles as _circles, fleet_run as _run
 
 
 def test_rejections_before_any_hip_call():
@@ -111,7 +98,6 @@ def test_selection_against_an_independent_sort():
             for keep in (0, 1, 13, 16):
                 within, chosen, _, _ = FM.select(d2, r, reach, keep)
                 assert (within, chosen) == _independent(pos, r, reach, keep), (n, r, keep)
-    lattice = [(i / 32.0, j / 32.0) for j in range(4) for i in range(5)][:19] + [(8 / 32.0, 0.0)]
     d2 = FM.d2_row(lattice, 0)
     assert d2[19] == 0.25 * 0.25
     within, chosen, edge, gap = FM.select(d2, 0, 0.25, 13)

@@ -12,121 +12,30 @@ margin between any state and any rim above ranking.MARGIN, the margin between
 any distance and the reach, the gap at a capped selection's boundary — before
 any kernel is looked at; the exact-tie case says where it does not.  The
 robots have the reference's 11 x 41 grid unless a case says otherwise."""
-import math
-
 import numpy as np
 import pytest
-import torch
 
 import fleet_model as FM
+import robots_bench as RB
 import robots_cases as RC
 import robots_model as RM
 import robots_obstacle_cases as OC
 import robots_obstacle_model as OM
 from diplomjourney_amd.abi import MPC_EP_ARRIVED
 from diplomjourney_amd.device_episodes import DeviceEpisodes, DeviceFleet, fleet_reach
-from diplomjourney_amd.episode_config import reference_episode_config, tree_episode_config
+from diplomjourney_amd.episode_config import tree_episode_config
+from fleet_cases import (CROSSING, CROWD_STATIC, LATTICE, NEAR, RING_CLEARANCE, SPLIT, cloud_20,
+                         cloud_520, crowd, parked, ring, robot)
 from ranking import MARGIN
+from robots_bench import (fleet_against as against, fleet_check as check,
+                          fleet_device_run as device_run, fleet_model as model)
 
 pytestmark = pytest.mark.gpu
-
-
-def robot(start, target, L=0.5, heading=None, v=0.5):
-    """A robot of the reference's configuration (11 x 41 grid, delta_t = 0.05,
-    arrival within sqrt(0.001)), no operator events, run_math_model.py's stuck
-    rule; headed at its target unless told otherwise."""
-    if heading is None:
-        heading = math.atan2(target[1] - start[1], target[0] - start[0])
-    c = reference_episode_config(start=(start[0], start[1], heading, v, 0.0), target=target,
-                                 enumerate=True)
-    c.L = L
-    c.p_turn_right = c.p_turn_left = c.p_new_target = 0
-    c.stop_rule = 1
-    return c
-
-
-def parked(at, make=robot):
-    """A robot that starts on its target: stopped at reset, an obstacle for good."""
-    return make(at, at, heading=0.0)
-
-
-def device_run(engine, cfgs, n_steps, integ, clearance, reach, static, launches, cap):
-    """DeviceFleet over `launches` -> the final (state, log, progress) bytes and
-    per launch (read_blocked(), neighbour table, board bytes)."""
-    eps = DeviceFleet(engine, cfgs, clearance, n_steps, integ, log_capacity=cap, obstacles=static,
-                      reach=reach)
-    eps.n_blocked.fill_(77)          # (zeroed by the entry, then added to)
-    eps.neighbours.fill_(55)         # (every row written by the last launch)
-    per = []
-    for k in launches:
-        eps.run(k)
-        per.append((eps.read_blocked(), eps.neighbours.cpu().numpy().copy(),
-                    eps.board.cpu().numpy().tobytes()))
-    torch.cuda.synchronize()
-    assert eps.call0 == sum(launches)
-    return (eps.state.cpu().numpy().tobytes(), eps.log.cpu().numpy().tobytes(),
-            eps.progress.cpu().numpy().tobytes()), per
-
-
-def model(cfgs, n_steps, integ, clearance, reach, static, n_calls, ties=False):
-    """The fleet's model over n_calls, its margins asserted (ties: the case is
-    about exact ties at the reach and at the cap, so those two are not)."""
-    reach = fleet_reach(cfgs, n_steps, clearance) if reach is None else reach
-    F = FM.Fleet(cfgs, n_steps, integ, clearance, reach, static).run(n_calls, device=True)
-    assert F.margin() > MARGIN, F.margin()
-    if not ties:
-        assert F.edge > MARGIN and F.gap > FM.CAP_GAP, (F.edge, F.gap)
-    return F
-
-
-def against(F, cfgs, cap, launches, got, per, name):
-    """The device's bytes against the model's."""
-    case = dict(cfgs=cfgs, cap=cap, launches=launches, name=name)
-    bad = RM.compare(case, *got, F.models, F.recs)
-    assert not bad, f"{name}: {len(bad)} differences:\n" + "\n".join(bad[:8])
-    want = FM.launch_counts(F, launches)
-    done = 0
-    for i, ((blocked, neigh, board), w) in enumerate(zip(per, want)):
-        done += launches[i]
-        assert blocked.dtype == np.int64 and (blocked == w).all(), (
-            f"{name} run {i}: n_blocked device {blocked}, model {w}")
-        rows = np.flatnonzero((neigh != F.neighbours(done)).any(axis=1))
-        assert not len(rows), (f"{name} run {i}: neighbours of robots {rows[:4]}: device "
-                               f"{neigh[rows[:4]]}, model {F.neighbours(done)[rows[:4]]}")
-        assert board == F.board(done), f"{name} run {i}: the pose board"
-
-
-def check(engine, cfgs, n_steps, integ, clearance, launches, reach=None, static=(), cap=16,
-          precondition=None, ties=False, name="fleet"):
-    F = model(cfgs, n_steps, integ, clearance, reach, static, sum(launches), ties)
-    if precondition:
-        precondition(F)
-    got, per = device_run(engine, cfgs, n_steps, integ, clearance, reach, static, launches, cap)
-    against(F, cfgs, cap, launches, got, per, name)
-    return F, got, per
 
 
 # ----------------------------------------------------------------------------
 # 1. the matrix: six robots on a ring
 # ----------------------------------------------------------------------------
-RING_CLEARANCE = 0.0213
-SPLIT = (1, 1, 1, 2, 5)
-RING_JITTER = (0.0, 0.05, -0.07, 0.11, 0.02, -0.04)
-
-
-def ring(L=0.5, radius=0.17):
-    """Six robots on a ring, each with its target diametrically opposite: they
-    meet in the middle after six calls (0.025 per call).  The ring is a little
-    irregular (radius + 0.012 j, the angles jittered), so that the robots do
-    not all do the same and a rim cuts through a step's candidates."""
-    out = []
-    for j in range(6):
-        a = 0.2 + 2 * math.pi * j / 6 + RING_JITTER[j]
-        p = ((radius + 0.012 * j) * math.cos(a), (radius + 0.012 * j) * math.sin(a))
-        out.append(robot(p, (-p[0], -p[1]), L))
-    return out
-
-
 def ring_interacts(F):
     assert any(p[0] >= 1 for p in F.picks[0]), F.picks[0]
     assert sum(sum(M.blocked_steps) for M in F.models) > 0
@@ -148,7 +57,7 @@ def test_ring_matrix(engine, integ, n_steps, L):
     one, per1 = device_run(engine, cfgs, n_steps, integ, RING_CLEARANCE, None, (), (10,), 16)
     assert one == got
     against(F, cfgs, 16, (10,), one, per1, "ring, one run(10)")
-    assert (per1[0][0] == sum(p[0] for p in per)).all()
+    assert (per1[0].blocked == sum(p.blocked for p in per)).all()
 
 
 def test_reach_beyond_the_horizon_changes_nothing(engine):
@@ -186,25 +95,11 @@ def test_two_robots_swap_places(engine, integ):
 # ----------------------------------------------------------------------------
 # 3. the crowd and the cap
 # ----------------------------------------------------------------------------
-CROWD_STATIC = ((0.16, 0.05, 0.0213), OC.FILLERS[0], OC.FILLERS[1])
-
-
-def crowd(points):
-    """Every robot headed the same way at a far target of its own."""
-    return [robot(p, (p[0] + 3.0, p[1] + 1.0)) for p in points]
-
-
 @pytest.mark.parametrize("integ", ("qk21", "rect+cum"))
 def test_crowd_above_the_cap(engine, integ):
     """Twenty robots inside one reach and three static circles: K = 13 of the
     19 others are chosen, per robot, and the table is full."""
-    rng = np.random.default_rng(20261021)
-    pts = []
-    while len(pts) < 20:           # a cloud of radius 0.12, nobody nearer than 0.03 to another
-        p = rng.uniform(-0.12, 0.12, 2)
-        if np.hypot(*p) < 0.12 and all(np.hypot(*(p - q)) > 0.03 for q in pts):
-            pts.append(p)
-    cfgs = crowd([(float(p[0]), float(p[1])) for p in pts])
+    cfgs = cloud_20()
 
     def capped(F):
         assert F.keep == 13
@@ -221,13 +116,7 @@ def test_crowd_across_the_scan_chunks(engine):
     256 entries at a time (two full chunks and one of 8), every robot has more
     than 16 others within reach, and its 16 nearest come from all three
     chunks — the kept list is merged with every chunk's."""
-    rng = np.random.default_rng(20261022)
-    pts = []
-    while len(pts) < 520:          # nobody nearer than 0.03 to another
-        p = rng.uniform(0.0, 1.0, 2)
-        if all(np.hypot(*(p - q)) > 0.03 for q in pts):
-            pts.append(p)
-    cfgs = crowd([(float(p[0]), float(p[1])) for p in pts])
+    cfgs = cloud_520()
 
     def spread(F):
         assert F.keep == 16 and all(p[0] > 16 and len(p[1]) == 16 for p in F.picks[0])
@@ -237,9 +126,6 @@ def test_crowd_across_the_scan_chunks(engine):
 
     check(engine, cfgs, 3, "rect+cum", 0.0113, (1, 1), reach=0.3, cap=4, precondition=spread,
           name="520 robots")
-
-
-LATTICE = [(i / 32.0, j / 32.0) for j in range(4) for i in range(5)][:19] + [(8 / 32.0, 0.0)]
 
 
 def test_ties_at_the_cap_and_the_reach(engine):
@@ -291,18 +177,10 @@ def test_ended_robots_stay_obstacles(engine, integ):
 # ----------------------------------------------------------------------------
 # 5. equivalences with what exists
 # ----------------------------------------------------------------------------
-NEAR = (0.05, 0.02, 0.0313)        # a static circle the ring's robots meet
-
-
 def stepwise(eps, n):
     """run(1) n times -> (state, log, progress) bytes and the blocked counts."""
-    blocked = []
-    for _ in range(n):
-        eps.run(1)
-        blocked.append(eps.read_blocked())
-    torch.cuda.synchronize()
-    return (eps.state.cpu().numpy().tobytes(), eps.log.cpu().numpy().tobytes(),
-            eps.progress.cpu().numpy().tobytes()), np.array(blocked)
+    blocked = RB.run_launches(eps, (1,) * n, lambda e: e.read_blocked())
+    return RB.snapshot(eps), np.array(blocked)
 
 
 @pytest.mark.parametrize("integ", ("qk21", "rect+cum"))
@@ -399,10 +277,6 @@ def test_the_frame_moves_with_the_robot(engine, integ, L):
 # ----------------------------------------------------------------------------
 # 8. the driver
 # ----------------------------------------------------------------------------
-CROSSING = [(0.0, 0.0, math.pi / 4, 0.3, 0.3), (0.3, 0.0, 3 * math.pi / 4, 0.0, 0.3),
-            (0.3, 0.3, -3 * math.pi / 4, 0.0, 0.0), (0.0, 0.3, -math.pi / 4, 0.3, 0.0)]
-
-
 def test_run_tree_fleet_equals_the_model(engine):
     """run_tree_fleet with four starts that cross in the middle of a square:
     the model's records and stop names, several host calls of eight fleet

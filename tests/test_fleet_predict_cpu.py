@@ -1,42 +1,20 @@
 """The predicted fleet call (mpc_episodes_fleet_run_predicted) without a GPU:
 what the entry rejects before any HIP call, the motion board's size, the
-model's per-step mask (tests/fleet_motion_model.py) against an independent
+model's per-step mask (MotionRobotModel, tests/fleet_model.py) against an independent
 brute force, the host build of the device's centre function against numpy,
 fleet_reach(predict=True) against its formula, and the follow case's
 precondition on the models alone."""
-import ctypes
 import math
 
 import numpy as np
 
 import fleet_model as FM
-import fleet_motion_model as MM
 import robots_cases as RC
+import robots_model as RM
 from diplomjourney_amd import abi, native
 from diplomjourney_amd.device_episodes import fleet_reach
-from diplomjourney_amd.episode_config import reference_episode_config
-
-FAKE = ctypes.c_void_p(0x1000)
-
-
-def _circles(*rows):
-    return abi.make_obstacles(rows)[0]
-
-
-def _args(obs=None, n=0, state=FAKE, board=FAKE, call0=0, clearance=0.1, reach=0.3, n_robots=1,
-          n_steps=3, integ=0, n_calls=1, log=None, cap=0):
-    return (state, board), (call0, obs, n, clearance, reach, n_robots, n_steps, integ, n_calls, log,
-                            cap, None, None, None, None)
-
-
-def _run(L, *a, motion=FAKE, **kw):
-    head, rest = _args(*a, **kw)
-    return L.mpc_episodes_fleet_run_predicted(*head, motion, *rest)
-
-
-def _plain(L, *a, **kw):
-    head, rest = _args(*a, **kw)
-    return L.mpc_episodes_fleet_run(*head, *rest)
+from fleet_cases import (FAKE, FOLLOW_CLEARANCE, circles as _circles, fleet_run as _plain,
+                         fleet_run_predicted as _run, follow)
 
 
 def test_rejections_before_any_hip_call():
@@ -88,13 +66,13 @@ def test_centre_is_numpys():
     d = np.concatenate([rng.uniform(-0.05, 0.05, 500), [0.2, 1e299, 1e-308, 0.1]])
     fused = 0
     for j in (0, 1, 2, 3, 4, 31, 32):
-        got = MM.centres(x, d, j)
+        got = FM.centres(x, d, j)
         assert (got == x + np.float64(j) * d).all(), j
         exact = np.array([float(np.longdouble(a) + np.longdouble(j) * np.longdouble(b))
                           for a, b in zip(x, d)])
         fused += int((got != exact).sum())
     assert fused > 0, "no input tells two roundings from one"
-    assert (MM.centres(x, d, 0) == x).all() and (MM.centres(x, np.zeros(len(x)), 7) == x).all()
+    assert (FM.centres(x, d, 0) == x).all() and (FM.centres(x, np.zeros(len(x)), 7) == x).all()
 
 
 def _brute(states, static, moving, n_steps):
@@ -127,9 +105,8 @@ def test_per_step_mask_against_brute_force():
         static = [(last[0] + 0.5, last[1], 0.01)]
         moving = [(last[0] - n_steps * d[0], last[1] - n_steps * d[1], d[0], d[1], 0.0051),
                   (mid[0] - 2 * 0.002, mid[1] - 2 * 0.001, 0.002, 0.001, 0.0043)]
-        M = MM.MotionRobotModel(cfg, n_steps, integ, static)
+        M = FM.MotionRobotModel(cfg, n_steps, integ, static)
         M.moving = moving
-        import robots_model as RM
         v, b = RM.enumerate_controls(V, B, n_steps)
         scored = M.score(states, np.array(costs, dtype=np.float64), v, b)
         mask = M.masks[0][0]
@@ -139,7 +116,7 @@ def test_per_step_mask_against_brute_force():
         assert (np.isinf(scored) == (mask | np.isinf(costs))).all()
         assert (M.hits[0].any(axis=(0, 1)) == mask).all()
         assert (M.masks[0][1] == M.hits[0][:-1].any(axis=(0, 1))).all()
-        for name, mult in MM.WRONG.items():
+        for name, mult in FM.WRONG.items():
             count, _, wm = M.wrong[name][0]
             want = np.zeros(len(mask), dtype=bool)
             for j in range(1, n_steps + 1):      # (step j alone, the circle moved mult times)
@@ -161,25 +138,6 @@ def test_predicted_reach_is_its_formula():
     assert fleet_reach([slow], 3, 0.07) == 3 * 0.1 * 1.0 * (1.0 + 2.0 ** -40) + 0.07
 
 
-def robot(start, target, L=0.5, heading=None, v=0.5):
-    """test_fleet_gpu.robot (that module is marked gpu as a whole)."""
-    if heading is None:
-        heading = math.atan2(target[1] - start[1], target[0] - start[0])
-    c = reference_episode_config(start=(start[0], start[1], heading, v, 0.0), target=target,
-                                 enumerate=True)
-    c.L = L
-    c.p_turn_right = c.p_turn_left = c.p_new_target = 0
-    c.stop_rule = 1
-    return c
-
-
-FOLLOW = dict(clearance=0.0513, n_steps=3)
-
-
-def follow():
-    return [robot((0.0, 0.0), (0.8, 0.0)), robot((0.09, 0.004), (0.8, 0.01))]
-
-
 def test_follow_precondition_on_the_models():
     """A follower behind a leader: the standing circle covers the follower's
     whole horizon, so the standing model's follower has every candidate
@@ -187,10 +145,11 @@ def test_follow_precondition_on_the_models():
     the prediction only call 0 is blocked (nobody has moved yet) and the
     follower runs all ten calls.  The motion list is what the boards say."""
     cfgs = follow()
-    reach = fleet_reach(cfgs, 3, FOLLOW["clearance"], predict=True)
-    S = FM.Fleet(cfgs, 3, "rect+cum", FOLLOW["clearance"], reach).run(10, device=False)
+    reach = fleet_reach(cfgs, 3, FOLLOW_CLEARANCE, predict=True)
+    S = FM.Fleet(cfgs, 3, "rect+cum", FOLLOW_CLEARANCE, reach).run(10, device=False)
     assert S.models[0].calls == 2 and S.models[0].stop and S.models[0].blocked_steps == [451, 451]
-    P = MM.MotionFleet(cfgs, 3, "rect+cum", FOLLOW["clearance"], reach).run(10, device=False)
+    P = FM.Fleet(cfgs, 3, "rect+cum", FOLLOW_CLEARANCE, reach, predict=True).run(10,
+                                                                                 device=False)
     M = P.models[0]
     assert M.calls == 10 and not M.stop and M.blocked_steps[0] == 451
     assert all(n < 451 for n in M.blocked_steps[1:])

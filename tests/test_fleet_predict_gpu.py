@@ -6,90 +6,36 @@ The pattern is test_fleet_gpu.py's: every comparison is robots_model.compare on
 the whole state tensor, every log ring and the progress records, plus, after
 every run(), read_blocked(), the neighbour table, both sides of the pose board
 and both sides of the motion board with `==`, against
-tests/fleet_motion_model.py.  Every case first asserts its preconditions on
+tests/fleet_model.py's Fleet(predict=True).  Every case first asserts its preconditions on
 that model — the margin between any state and any MOVING rim above
 ranking.MARGIN, the margins at the reach and the cap, and what the case is
 about — before any kernel is looked at.  The model also scores every step
 under each wrong multiplier of the displacement (0, j - 1, j + 1, N, 1): the
 ring matrix asserts that each of them would have given other counts and other
 winners."""
+import functools
 import math
 
 import numpy as np
 import pytest
-import torch
 
 import fleet_model as FM
-import fleet_motion_model as MM
+import robots_bench as RB
 import robots_cases as RC
-import test_fleet_gpu as TF
 from diplomjourney_amd.abi import MPC_EP_ARRIVED, MPC_MAX_OBSTACLES, MPC_MAX_STEPS
-from diplomjourney_amd.device_episodes import DeviceFleet, fleet_reach
+from diplomjourney_amd.device_episodes import fleet_reach
 from diplomjourney_amd.episode_config import tree_episode_config
-from ranking import MARGIN
+from fleet_cases import (CROSSING, FLAG_CLEARANCE, FOLLOW_CLEARANCE, RING_CLEARANCE, SPLIT,
+                         flagged_fleet, follow, long_crowd, parked, ring, robot)
+from robots_bench import fleet_against as against
 
 pytestmark = pytest.mark.gpu
 
 DEVICE = True        # the model's reciprocal estimates: the GPU's
-robot, parked = TF.robot, TF.parked
-
-
-def device_run(engine, cfgs, n_steps, integ, clearance, reach, static, launches, cap,
-               predict=True):
-    """DeviceFleet over `launches` -> the final (state, log, progress) bytes and
-    per launch (read_blocked(), neighbour table, board bytes, motion bytes)."""
-    eps = DeviceFleet(engine, cfgs, clearance, n_steps, integ, log_capacity=cap, obstacles=static,
-                      reach=reach, predict=predict)
-    eps.n_blocked.fill_(77)
-    eps.neighbours.fill_(55)
-    if predict:
-        eps.motion.fill_(0x5A)       # (side 0 zeroed by the entry before call 0, side 1 written)
-    per = []
-    for k in launches:
-        eps.run(k)
-        per.append((eps.read_blocked(), eps.neighbours.cpu().numpy().copy(),
-                    eps.board.cpu().numpy().tobytes(),
-                    eps.motion.cpu().numpy().tobytes() if predict else None))
-    torch.cuda.synchronize()
-    assert eps.call0 == sum(launches)
-    return (eps.state.cpu().numpy().tobytes(), eps.log.cpu().numpy().tobytes(),
-            eps.progress.cpu().numpy().tobytes()), per
-
-
-def model(cfgs, n_steps, integ, clearance, reach, static, n_calls, ties=False):
-    """The predicted fleet's model over n_calls, its margins asserted."""
-    reach = fleet_reach(cfgs, n_steps, clearance, predict=True) if reach is None else reach
-    F = MM.MotionFleet(cfgs, n_steps, integ, clearance, reach, static).run(n_calls, device=DEVICE)
-    assert F.margin() > MARGIN, F.margin()
-    if not ties:
-        assert F.edge > MARGIN and F.gap > FM.CAP_GAP, (F.edge, F.gap)
-    return F
-
-
-def against(F, cfgs, cap, launches, got, per, name):
-    """The device's bytes against the model's: test_fleet_gpu.against, and the
-    motion board after every run()."""
-    TF.against(F, cfgs, cap, launches, got, [p[:3] for p in per], name)
-    done = 0
-    for i, p in enumerate(per):
-        done += launches[i]
-        if p[3] != F.motion(done):
-            dev = np.frombuffer(p[3], dtype=np.float64).reshape(2, -1, 2)
-            want = np.frombuffer(F.motion(done), dtype=np.float64).reshape(2, -1, 2)
-            rows = np.argwhere((dev != want).any(axis=2))
-            raise AssertionError(f"{name} run {i}: the motion board, (side, robot) {rows[:4]}: "
-                                 f"device {[dev[s, r] for s, r in rows[:4]]}, "
-                                 f"model {[want[s, r] for s, r in rows[:4]]}")
-
-
-def check(engine, cfgs, n_steps, integ, clearance, launches, reach=None, static=(), cap=16,
-          precondition=None, ties=False, name="predicted fleet"):
-    F = model(cfgs, n_steps, integ, clearance, reach, static, sum(launches), ties)
-    if precondition:
-        precondition(F)
-    got, per = device_run(engine, cfgs, n_steps, integ, clearance, reach, static, launches, cap)
-    against(F, cfgs, cap, launches, got, per, name)
-    return F, got, per
+# the bench with the predicted entry (a call may still say predict=False)
+device_run = functools.partial(RB.fleet_device_run, predict=True)
+model = functools.partial(RB.fleet_model, predict=True)
+check = functools.partial(RB.fleet_check, predict=True, name="predicted fleet")
 
 
 def winners(F):
@@ -107,7 +53,7 @@ def ring_predicts(F):
     assert any(p[0] >= 1 for p in F.picks[0]), F.picks[0]
     assert any(0 < n < 451 for M in F.models for n in M.blocked_steps)
     won = winners(F)
-    for name in MM.WRONG:
+    for name in FM.WRONG:
         counts = sum(w[0] != n for M in F.models for w, n in zip(M.wrong[name], M.blocked_steps))
         wins = sum(w[1] != i for M, ww in zip(F.models, won) for w, i in zip(M.wrong[name], ww))
         assert counts >= 1 and wins >= 1, (name, counts, wins)
@@ -120,26 +66,19 @@ def test_ring_matrix(engine, integ, n_steps, L):
     """Ten predicted fleet calls as run(1) x 3 + run(2) + run(5) — odd and
     even call0, both boards' parity across entry calls — and as one run(10):
     the same bits, the model's."""
-    cfgs = TF.ring(L)
-    F, got, per = check(engine, cfgs, n_steps, integ, TF.RING_CLEARANCE, TF.SPLIT,
+    cfgs = ring(L)
+    F, got, per = check(engine, cfgs, n_steps, integ, RING_CLEARANCE, SPLIT,
                         precondition=ring_predicts, name=f"ring {integ} N={n_steps} L={L}")
-    one, per1 = device_run(engine, cfgs, n_steps, integ, TF.RING_CLEARANCE, None, (), (10,), 16)
+    one, per1 = device_run(engine, cfgs, n_steps, integ, RING_CLEARANCE, None, (), (10,), 16)
     assert one == got
     against(F, cfgs, 16, (10,), one, per1, "ring, one run(10)")
-    assert (per1[0][0] == sum(p[0] for p in per)).all()
-    assert per1[0][2:] == per[-1][2:]
+    assert (per1[0].blocked == sum(p.blocked for p in per)).all()
+    assert (per1[0].board, per1[0].motion) == (per[-1].board, per[-1].motion)
 
 
 # ----------------------------------------------------------------------------
 # 2. follow
 # ----------------------------------------------------------------------------
-FOLLOW_CLEARANCE = 0.0513
-
-
-def follow():
-    return [robot((0.0, 0.0), (0.8, 0.0)), robot((0.09, 0.004), (0.8, 0.01))]
-
-
 @pytest.mark.parametrize("integ", ("qk21", "rect+cum"))
 def test_follower_runs_behind_the_leader(engine, integ):
     """A follower behind a leader.  Standing circles stop it as stuck after two
@@ -168,15 +107,16 @@ def test_call_0_is_the_fleet_call(engine, integ):
     explicit reach): the same state, log, progress, blocked counts, neighbours
     and pose board; the motion board's side 0 zeroed, its side 1 the
     displacements."""
-    cfgs = TF.ring()
-    reach = fleet_reach(cfgs, 3, TF.RING_CLEARANCE, predict=True)
-    a, pa = device_run(engine, cfgs, 3, integ, TF.RING_CLEARANCE, reach, (), (1,), 16)
-    b, pb = device_run(engine, cfgs, 3, integ, TF.RING_CLEARANCE, reach, (), (1,), 16,
+    cfgs = ring()
+    reach = fleet_reach(cfgs, 3, RING_CLEARANCE, predict=True)
+    a, pa = device_run(engine, cfgs, 3, integ, RING_CLEARANCE, reach, (), (1,), 16)
+    b, pb = device_run(engine, cfgs, 3, integ, RING_CLEARANCE, reach, (), (1,), 16,
                        predict=False)
     assert a == b
-    assert (pa[0][0] == pb[0][0]).all() and (pa[0][1] == pb[0][1]).all() and pa[0][2] == pb[0][2]
-    board = np.frombuffer(pa[0][2], dtype=np.float64).reshape(2, 6, 2)
-    motion = np.frombuffer(pa[0][3], dtype=np.float64).reshape(2, 6, 2)
+    assert (pa[0].blocked == pb[0].blocked).all()
+    assert (pa[0].neighbours == pb[0].neighbours).all() and pa[0].board == pb[0].board
+    board = np.frombuffer(pa[0].board, dtype=np.float64).reshape(2, 6, 2)
+    motion = np.frombuffer(pa[0].motion, dtype=np.float64).reshape(2, 6, 2)
     assert (motion[0] == 0.0).all() and (motion[1] == board[1] - board[0]).all()
     assert (motion[1] != 0.0).any(axis=1).all()
 
@@ -201,7 +141,8 @@ def test_parked_neighbours_equal_the_fleet_call(engine, integ):
                        predict=False)
     assert a == b
     for x, y in zip(pa, pb):
-        assert (x[0] == y[0]).all() and (x[1] == y[1]).all() and x[2] == y[2]
+        assert (x.blocked == y.blocked).all() and (x.neighbours == y.neighbours).all()
+        assert x.board == y.board
     against(F, cfgs, 16, (1,) * 8, a, pa, f"parked {integ}")
 
 
@@ -235,29 +176,6 @@ def test_ended_robots_publish_zero(engine, integ):
 # ----------------------------------------------------------------------------
 # 6. flagged candidates
 # ----------------------------------------------------------------------------
-FLAG_CLEARANCE = 0.0083
-
-
-def flagged_fleet(integ, n_steps):
-    """Two robots of robots_cases' case B (one of each set) and a moving
-    neighbour (the reference's robot, 0.025 a call) started where its circle
-    at step N of fleet call 1 lies on a flagged candidate's state after step N
-    of robot 0: the robots' lone runs give that state and the neighbour's
-    first displacement; the fleet's model then says whether it came so."""
-    base = RC.case_b(integ, n_steps, 0.5)
-    a, a2 = base["cfgs"][0], base["cfgs"][21]
-    lone = MM.MotionFleet([a], n_steps, integ, FLAG_CLEARANCE, 0.0).run(2, device=DEVICE)
-    M = lone.models[0]
-    k = int(np.flatnonzero(np.abs(M.betas[1]) > RC.K_TAN_MAX)[0])
-    at = (float(M.states[1][n_steps - 1, 0, k]), float(M.states[1][n_steps - 1, 1, k]))
-    u = (math.cos(2.3), math.sin(2.3))
-    q = MM.MotionFleet([robot((0.0, 0.0), (3 * u[0], 3 * u[1]))], n_steps, integ, FLAG_CLEARANCE,
-                       0.0).run(1, device=DEVICE)
-    d = q.motions[1][0]
-    p0 = (at[0] - (n_steps + 1) * d[0], at[1] - (n_steps + 1) * d[1])
-    return [a, a2, robot(p0, (p0[0] + 3 * u[0], p0[1] + 3 * u[1]))], k
-
-
 @pytest.mark.parametrize("n_steps", (3, 4))
 @pytest.mark.parametrize("integ", RC.MODES)
 def test_flagged_candidates_meet_the_moved_circle(engine, integ, n_steps):
@@ -265,7 +183,7 @@ def test_flagged_candidates_meet_the_moved_circle(engine, integ, n_steps):
     recompute's) is blocked by the moving neighbour's step-j circle, j >= 2,
     and by neither the standing circle nor the one of step j - 1: the safe
     recompute tests each state against its own step's world table."""
-    cfgs, k = flagged_fleet(integ, n_steps)
+    cfgs, k = flagged_fleet(integ, n_steps, device=DEVICE)
 
     def flagged(F):
         M = F.models[0]
@@ -289,23 +207,6 @@ def test_flagged_candidates_meet_the_moved_circle(engine, integ, n_steps):
 # ----------------------------------------------------------------------------
 # 7. the longest horizon: the tables' second pass
 # ----------------------------------------------------------------------------
-def long_crowd():
-    """18 robots with case B's 3 x 7 grid in one cloud, headed one way."""
-    rng = np.random.default_rng(20261024)
-    pts = []
-    while len(pts) < 18:
-        p = rng.uniform(-0.12, 0.12, 2)
-        if np.hypot(*p) < 0.12 and all(np.hypot(*(p - q)) > 0.03 for q in pts):
-            pts.append(p)
-    out = []
-    for p in pts:
-        x, y = float(p[0]), float(p[1])
-        out.append(RC.base_cfg(start=(x, y, math.atan2(1.0, 3.0), 0.5, 0.0),
-                               target=(x + 3.0, y + 1.0), ratio_v=1.0, delta_beta=0.4,
-                               ratio_beta=3.0, beta_bound=1.3))
-    return out
-
-
 @pytest.mark.parametrize("integ", ("qk21", "rect+cum"))
 def test_longest_horizon_fills_the_tables_in_two_passes(engine, integ):
     """n_steps = MPC_MAX_STEPS and a full table: 32 x 16 = 512 entries, formed
@@ -344,7 +245,8 @@ def test_reach_beyond_two_horizons_changes_nothing(engine):
     assert blockers and max(blockers) >= short, (max(blockers, default=None), short)
     a, pa = device_run(engine, cfgs, 3, "qk21", FOLLOW_CLEARANCE, None, (), (10,), 16)
     b, pb = device_run(engine, cfgs, 3, "qk21", FOLLOW_CLEARANCE, 2 * reach, (), (10,), 16)
-    assert a == b and pa[0][2:] == pb[0][2:] and (pa[0][0] == pb[0][0]).all()
+    assert a == b and (pa[0].board, pa[0].motion) == (pb[0].board, pb[0].motion)
+    assert (pa[0].blocked == pb[0].blocked).all()
     against(F, cfgs, 16, (10,), a, pa, "reach")
     against(F2, cfgs, 16, (10,), b, pb, "twice the reach")
 
@@ -359,11 +261,11 @@ def test_run_tree_fleet_predicts(engine):
     from diplomjourney_amd import math_model_tree as mmt
     from diplomjourney_amd import run_math_model as rmm
     mmt.reset_state()
-    cfgs = [tree_episode_config(s, 24) for s in TF.CROSSING]
+    cfgs = [tree_episode_config(s, 24) for s in CROSSING]
     F = model(cfgs, 3, "qk21", 0.0513, None, (), 24)
     assert sum(sum(M.blocked_steps) for M in F.models) > 0 and all(M.stop for M in F.models)
     stats = {}
-    got = rmm.run_tree_fleet(TF.CROSSING, 0.0513, max_calls=24, engine=engine, stats=stats, chunk=8,
+    got = rmm.run_tree_fleet(CROSSING, 0.0513, max_calls=24, engine=engine, stats=stats, chunk=8,
                              predict=True)
     for r, (records, stop) in enumerate(got):
         assert stop == rmm._stop_name(F.models[r].stop), r
@@ -371,8 +273,8 @@ def test_run_tree_fleet_predicts(engine):
     assert stats["steps"] == max(M.calls for M in F.models)
     assert stats["candidates"] == sum(M.candidates for M in F.models)
     assert stats["blocked"] == sum(sum(M.blocked_steps) for M in F.models)
-    S = TF.model(cfgs, 3, "qk21", 0.0513, None, (), 24)
-    standing = rmm.run_tree_fleet(TF.CROSSING, 0.0513, max_calls=24, engine=engine, chunk=8)
+    S = model(cfgs, 3, "qk21", 0.0513, None, (), 24, predict=False)
+    standing = rmm.run_tree_fleet(CROSSING, 0.0513, max_calls=24, engine=engine, chunk=8)
     for r, (records, stop) in enumerate(standing):
         assert stop == rmm._stop_name(S.models[r].stop), r
         assert records == [[q[k] for k in ("x", "y", "phi", "v", "beta")] for q in S.recs[r]], r

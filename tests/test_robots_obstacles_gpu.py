@@ -15,9 +15,8 @@ any kernel is looked at (tests/test_robots_obstacles_cpu.py checks the same
 with the IEEE replica)."""
 import numpy as np
 import pytest
-import torch
 
-import episode_state as ES
+import robots_bench as RB
 import robots_cases as RC
 import robots_model as RM
 import robots_obstacle_cases as OC
@@ -28,38 +27,19 @@ from diplomjourney_amd.device_episodes import DeviceEpisodes
 pytestmark = pytest.mark.gpu
 
 
-def device_run(engine, case, circles, cls=DeviceEpisodes):
-    """The case's launches with `circles` -> (state, log, progress) bytes and
-    read_blocked() after every launch."""
-    eps = cls(engine, case["cfgs"], case["n_steps"], case["integ"], log_capacity=case["cap"],
-              obstacles=circles)
-    assert ES.robots_state_bytes(eps.R) == eps.state.numel()
-    eps.n_blocked.fill_(77)          # (written, not accumulated)
-    blocked = []
-    for k in case["launches"]:
-        eps.run(k)
-        blocked.append(eps.read_blocked())
-    torch.cuda.synchronize()
-    return (eps.state.cpu().numpy().tobytes(), eps.log.cpu().numpy().tobytes(),
-            eps.progress.cpu().numpy().tobytes(), blocked)
-
-
 def check(engine, case, count, precondition=None):
     """The model run (shared by the counts of one case), its preconditions,
-    then the device against it."""
+    then the device against it -> the models, their records and the device's
+    (state, log, progress) bytes with read_blocked() after every launch."""
     models, recs, first = OC.model_run(case, device=True)
     assert min(M.margin for M in models) > OC.MARGIN, min(M.margin for M in models)
     if precondition:
         precondition(models, recs, first)
-    got = device_run(engine, case, OC.table(case, count))
-    bad = RM.compare(case, *got[:3], models, recs)
-    assert not bad, f"{case['name']} x{count}: {len(bad)} differences:\n" + "\n".join(bad[:8])
-    want = OM.launch_counts(models, case["launches"])
-    for i, (g, w) in enumerate(zip(got[3], want)):
-        assert g.dtype == np.int64 and (g == w).all(), (
-            f"{case['name']} x{count} launch {i}: n_blocked of robots "
-            f"{np.flatnonzero(g != w)[:8]}: device {g[g != w][:8]}, model {w[g != w][:8]}")
-    return models, recs, got
+    got, blocked, _ = RB.episodes_run(engine, case, OC.table(case, count))
+    name = f"{case['name']} x{count}"
+    RB.assert_model(dict(case, name=name), got, models, recs)
+    RB.assert_counts(name, blocked, OM.launch_counts(models, case["launches"]))
+    return models, recs, (*got, blocked)
 
 
 # ----------------------------------------------------------------------------
@@ -166,11 +146,11 @@ def test_obstacle_entry_without_circles(engine, integ):
 
     case = dict(RC.case_b(integ, 3, 0.5), launches=(2, 4), name=f"zero circles {integ}")
     models, recs, _ = RC.model_run(case, device=True)
-    plain = device_run(engine, case, ())
-    entry = device_run(engine, case, (), ObstacleEntry)
-    assert entry[:3] == plain[:3]
-    assert not RM.compare(case, *entry[:3], models, recs)
-    assert all((b == 0).all() for b in entry[3] + plain[3])
+    plain, none, _ = RB.episodes_run(engine, case, ())
+    entry, zeros, _ = RB.episodes_run(engine, case, (), ObstacleEntry)
+    assert entry == plain
+    assert not RM.compare(case, *entry, models, recs)
+    assert all((b == 0).all() for b in zeros + none)
 
 
 # ----------------------------------------------------------------------------

@@ -20,39 +20,25 @@ never writes (its grid lives in LDS), are compared like every other field:
 they must hold what k_episodes_reset left, 0.  The comparison and its report
 are robots_model.compare (checked on the CPU with planted differences)."""
 import pytest
-import torch
 
-import episode_state as ES
+import robots_bench as RB
 import robots_cases as RC
 import robots_model as RM
 from diplomjourney_amd.abi import (LOG_BYTES, MPC_EP_ARRIVED, MPC_EP_BREAK, MPC_EP_EVENT,
                                    MPC_EP_LIMIT, MPC_EP_STALE, MPC_EP_STUCK, MpcEpisodeLog)
-from diplomjourney_amd.device_episodes import DeviceEpisodes
 
 pytestmark = pytest.mark.gpu
 
 
-def device_run(engine, case):
-    """The case's launches -> (state, log, progress) bytes and read_logs()."""
-    eps = DeviceEpisodes(engine, case["cfgs"], case["n_steps"], case["integ"],
-                         log_capacity=case["cap"])
-    assert ES.robots_state_bytes(eps.R) == eps.state.numel()
-    for k in case["launches"]:
-        eps.run(k)
-    torch.cuda.synchronize()
-    logs = eps.read_logs()
-    return (eps.state.cpu().numpy().tobytes(), eps.log.cpu().numpy().tobytes(),
-            eps.progress.cpu().numpy().tobytes(), logs)
-
-
 def check(engine, case):
+    """-> the models, their records and the device's (state, log, progress)
+    bytes with read_logs() behind them."""
     models, recs, first = RC.model_run(case, device=True)
     if case.get("every_candidate") and sum(case["launches"]):   # before any kernel is looked at
         assert RC.excluded(case, first) == []
-    got = device_run(engine, case)
-    bad = RM.compare(case, *got[:3], models, recs)
-    assert not bad, f"{case['name']}: {len(bad)} differences:\n" + "\n".join(bad[:8])
-    return models, recs, got
+    got, _, eps = RB.episodes_run(engine, case)
+    RB.assert_model(case, got, models, recs)
+    return models, recs, (*got, eps.read_logs())
 
 
 @pytest.mark.parametrize("n_steps,L", RC.SHAPES_A)
