@@ -72,6 +72,13 @@ template <class Obs, class = void>
 struct motion_hook : std::false_type {};
 template <class Obs>
 struct motion_hook<Obs, std::void_t<decltype(Obs::kMotion)>> : std::true_type {};
+// A motion hook that declares kPlan takes the neighbours' circles from their
+// own plans (FleetPlanObs): on exit it publishes two layers of the robot's
+// StaleTraj instead of the displacement.
+template <class Obs, class = void>
+struct plan_hook : std::false_type {};
+template <class Obs>
+struct plan_hook<Obs, std::void_t<decltype(Obs::kPlan)>> : std::true_type {};
 
 // Two kernel arguments made live where this is called: their scalar loads are
 // issued together and waited for once.  A fleet launch's arguments span two
@@ -373,6 +380,12 @@ __device__ __forceinline__ int64_t block_sum_i64(int64_t n) {
 // step: the pair rollout hands the hook the step's index, and the block writes
 // the robot's displacement to the motion board's other side on exit.  Every
 // such statement sits under `if constexpr (kMotion)` (motion_hook).
+// A planned fleet call (mpc_episodes_fleet_run_planned; Obs = FleetPlanObs, W =
+// FleetPlanArgs) is a predicted one whose tables follow the neighbours' plans:
+// the kernel notes m at the start of the step beside from_x and, on exit, hands
+// the hook the step's status, that m, the staged StaleTraj and the position for
+// the plan board's other side.  Every such statement sits under
+// `if constexpr (kPlan)` (plan_hook).
 template <int INTEG, int ROT, class Obs = NoObs, class... W, class... B>
 __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
     W... world, const mpc_episode_config_t* __restrict__ cfgs, RobotState* __restrict__ robots,
@@ -382,6 +395,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
                 "the table and the count come with a hook, and only with one");
   constexpr bool kFleet = fleet_hook<Obs>::value;
   constexpr bool kMotion = motion_hook<Obs>::value;
+  constexpr bool kPlan = plan_hook<Obs>::value;
   if constexpr (kFleet) kernarg_touch((world, ...).n, (count, ...));   // (both lines, one wait)
   const int r = blockIdx.x;
   const mpc_episode_config_t& c = cfgs[r];
@@ -411,6 +425,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
   [[maybe_unused]] int64_t n_blk = 0;   // this lane's blocked candidates
   [[maybe_unused]] bool fleet_step = false;   // (kFleet) the robot took a step in this launch
   [[maybe_unused]] double from_x = 0.0, from_y = 0.0;   // (kMotion) where that step began
+  [[maybe_unused]] int from_m = 0;                        // (kPlan) the finishing count m then
   TL_EP_BEGIN();
   for (int call = 0; call < max_calls; ++call) {
     __syncthreads();
@@ -421,6 +436,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       obs.select((world, ...), r, Hs->x, Hs->y);
       fleet_step = true;
       if constexpr (kMotion) from_x = Hs->x, from_y = Hs->y;
+      if constexpr (kPlan) from_m = Hs->m;
     }
     if (threadIdx.x < 64) {
       int nv, nb;
@@ -585,7 +601,11 @@ __global__ __launch_bounds__(kBlock, 2) void k_episodes_run(
       if (n_blocked) n_blocked[r] += blocked_all;
       const EpisodeHead* Hs = reinterpret_cast<const EpisodeHead*>(s_head);
       (world, ...).board_out[r] = {Hs->x, Hs->y};   // where the robot stands after this call
-      if constexpr (kMotion)   // ... and how far the call moved it, if it goes on
+      if constexpr (kPlan)   // ... and where it means to go next, if it goes on with a winner
+        Obs::publish((world, ...), r, fleet_step && !s_stop && !(s_log.status & MPC_EP_STALE),
+                     from_m, *reinterpret_cast<const StaleTraj*>(&s_head[kHeadWords]), Hs->x,
+                     Hs->y);
+      else if constexpr (kMotion)   // ... and how far the call moved it, if it goes on
         Obs::publish((world, ...), r, fleet_step && !s_stop, from_x, from_y, Hs->x, Hs->y);
     } else if constexpr (Obs::kOn) {
       if (n_blocked) n_blocked[r] = blocked_all;

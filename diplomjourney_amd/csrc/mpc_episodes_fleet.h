@@ -32,6 +32,9 @@
 // FleetMotionObs, below: the hook of a predicted fleet call
 // (mpc_episodes_fleet_run_predicted), the same selection with one table per
 // horizon step, the neighbours' circles moved by their last displacement.
+// FleetPlanObs, below it: the hook of a planned fleet call
+// (mpc_episodes_fleet_run_planned), the same tables with the circles on the
+// neighbours' own plans, read from a plan board.
 #pragma once
 
 #include "mpc_episode_obs.h"
@@ -319,6 +322,97 @@ struct FleetMotionObs : FleetObs<ROT> {
 template <int ROT>
 __device__ __forceinline__ FleetMotionObs<ROT> episode_obs(FleetMotionObs<ROT>*) {
   FleetMotionObs<ROT> o;
+  o.world_at = lds_addr(fleet_step_world()->c);
+  o.loop_at = ROT == kRotCum ? lds_addr(fleet_step_frame()->c) : o.world_at;
+  return o;
+}
+
+// ---------------------------------------------------------------------------
+// A planned fleet call (mpc_episodes_fleet_run_planned): each chosen
+// neighbour's circle follows the neighbour's own plan, two points (a1, a2) read
+// from this call's side of the plan board — where the neighbour means to be
+// after this call and after the next: layers of its StaleTraj, the arc it
+// drives, or its position twice if it stands.  Step 1's centre is a1, step 2's
+// a2, step j >= 3's fleet_predict(a2, a2 - a1, j - 2) per coordinate.  The
+// selection, the per-step tables, form() and the lanes' tests are
+// FleetMotionObs'; only where a centre comes from differs.  The chosen
+// neighbours' entries are staged in LDS first — one 32-B load each, by the
+// first `len` threads, which form a2 - a1 there once — and the tables' entries
+// are formed from LDS: no entry waits for a global load of its own, and the
+// difference is not made N times.  k_fleet_plan_begin fills the board's side 0
+// before planned call 0: everybody stands.
+struct FleetPlanLds {
+  FleetPlan a[MPC_MAX_OBSTACLES];   // the chosen neighbours' entries
+  FleetPos d[MPC_MAX_OBSTACLES];    // a2 - a1
+};
+
+__device__ __forceinline__ FleetPlanLds* fleet_plan_lds() {
+  __shared__ FleetPlanLds s_fleet_plan;
+  return &s_fleet_plan;
+}
+
+__global__ void k_fleet_plan_begin(const FleetPos* __restrict__ board, int n,
+                                   FleetPlan* __restrict__ plan) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const FleetPos p = board[r];
+  plan[r] = FleetPlan{p.x, p.y, p.x, p.y};
+}
+
+template <int ROT>
+struct FleetPlanObs : FleetMotionObs<ROT> {
+  static constexpr bool kPlan = true;   // (the kernel: m at the start of the step, the plan write)
+
+  // FleetObs::select, the chosen neighbours' entries staged, then the per-step
+  // tables (entry e = (j - 1) * g4 + i: circle i of step j).
+  __device__ __forceinline__ void select(const FleetPlanArgs& A, int r, double x, double y) {
+    FleetObs<ROT>::select(A, r, x, y);
+    if (this->m == 0) {   // uniform: the call runs without circles
+      this->entries = 0;
+      return;
+    }
+    FleetLds* S = fleet_lds();
+    FleetPlanLds* P = fleet_plan_lds();
+    FleetStepTable* T = fleet_step_world();
+    const int g4 = this->groups() * kFleetGroup, n_static = A.n_static, m = this->m;
+    if (static_cast<int>(threadIdx.x) < m - n_static) {
+      const FleetPlan a = A.plan_in[S->idx[threadIdx.x]];
+      P->a[threadIdx.x] = a;
+      P->d[threadIdx.x] = FleetPos{a.x2 - a.x1, a.y2 - a.y1};
+    }
+    __syncthreads();
+    this->entries = A.n_steps * g4;
+    for (int e = threadIdx.x; e < this->entries; e += kBlock) {
+      const int j = e / g4, i = e - j * g4;
+      Circle cq = S->world[i];
+      if (i >= n_static && i < m) {
+        const FleetPlan a = P->a[i - n_static];
+        const FleetPos d = P->d[i - n_static];
+        cq.cx = j == 0 ? a.x1 : (j == 1 ? a.x2 : fleet_predict(a.x2, d.x, j - 1));
+        cq.cy = j == 0 ? a.y1 : (j == 1 ? a.y2 : fleet_predict(a.y2, d.y, j - 1));
+      }
+      T->c[j][i] = cq;
+    }
+    __syncthreads();
+  }
+
+  // Block r's entry of the plan board's out side (one thread).  plans: the
+  // robot took a step in this call, goes on after it, and the step had a
+  // winner; its entry is then layers min(k + 1, 2) and min(k + 2, 2) of its
+  // plan, k the layer the update returned (m0: m when the step began).
+  // Everyone else stands at (x, y).  Copies, no arithmetic.
+  __device__ __forceinline__ static void publish(const FleetPlanArgs& A, int r, bool plans, int m0,
+                                                 const StaleTraj& st, double x, double y) {
+    const int k = m0 == 2 ? 2 : (m0 == 1 ? 1 : 0);
+    const int k1 = k == 0 ? 1 : 2, k2 = 2;   // min(k + 1, 2); min(k + 2, 2) = 2 for every k
+    A.plan_out[r] = plans ? FleetPlan{st.ot[k1][0], st.ot[k1][1], st.ot[k2][0], st.ot[k2][1]}
+                          : FleetPlan{x, y, x, y};
+  }
+};
+
+template <int ROT>
+__device__ __forceinline__ FleetPlanObs<ROT> episode_obs(FleetPlanObs<ROT>*) {
+  FleetPlanObs<ROT> o;
   o.world_at = lds_addr(fleet_step_world()->c);
   o.loop_at = ROT == kRotCum ? lds_addr(fleet_step_frame()->c) : o.world_at;
   return o;

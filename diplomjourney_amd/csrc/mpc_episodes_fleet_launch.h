@@ -48,8 +48,32 @@ struct FleetMotionArgs : FleetArgs {
   int32_t n_steps;             // the horizon N: tables for steps 1..N
 };
 
+// One robot's entry of the plan board (32 B): where it means to be after the
+// next fleet call and after the one behind it — two layers of its StaleTraj,
+// or its position twice if it stands (mpc_episodes_fleet_run_planned).
+struct FleetPlan {
+  double x1, y1, x2, y2;
+};
+static_assert(sizeof(FleetPlan) == 32, "the plan board: 32 B per robot per side");
+
+// The plan board: two sides of n entries, the pose board's parity.
+inline size_t fleet_plan_bytes(int n) { return 2 * static_cast<size_t>(n) * sizeof(FleetPlan); }
+
+// A planned fleet launch's arguments (mpc_episodes_fleet_run_planned): the
+// fleet launch's, first and unchanged, then the plan board's sides and the
+// horizon, as FleetMotionArgs has the motion board's.
+struct FleetPlanArgs : FleetArgs {
+  const FleetPlan* plan_in;    // this call's side: every robot's next two plan points
+  FleetPlan* plan_out;         // the other side: block r writes entry r on exit
+  int32_t n_steps;             // the horizon N: tables for steps 1..N
+};
+
 // side 0 of the board from the robots' states
 void launch_fleet_begin(hipStream_t st, const RobotState* robots, int n_robots, FleetPos* board);
+
+// side 0 of the plan board from side 0 of the pose board: everybody stands
+// (x, y, x, y), before planned fleet call 0
+void launch_fleet_plan_begin(hipStream_t st, const FleetPos* board, int n_robots, FleetPlan* plan);
 
 // k_episodes_run<mode of `integrator`, FleetObs> for ONE MPC step of every
 // running robot (max_calls = 1), one block per robot; n_blocked[r] (or NULL) is
@@ -64,6 +88,12 @@ void launch_episodes_fleet_predicted(hipStream_t st, int32_t integrator, const F
                                      int n_robots, const mpc_episode_config_t* cfgs,
                                      RobotState* robots, mpc_episode_log_t* log, int cap,
                                      mpc_episodes_progress_t* progress, int64_t* n_blocked);
+
+// The same with FleetPlanObs: one PLANNED fleet call (A.plan_in / _out set).
+void launch_episodes_fleet_planned(hipStream_t st, int32_t integrator, const FleetPlanArgs& A,
+                                   int n_robots, const mpc_episode_config_t* cfgs,
+                                   RobotState* robots, mpc_episode_log_t* log, int cap,
+                                   mpc_episodes_progress_t* progress, int64_t* n_blocked);
 
 #ifdef MPC_TIMELINE
 // The second unit's copy of workload R's phase table (mpc_timeline.h: a table is

@@ -2,8 +2,9 @@
 // circle instantiations of the batched robots' episode kernel (k_episodes_run,
 // mpc_episodes.h, with the hooks of mpc_episodes_obs.h) and their launch, and
 // the fleet instantiations of the same kernel (the hooks of mpc_episodes_fleet.h:
-// FleetObs, and FleetMotionObs for the predicted fleet call),
-// the kernel that fills the pose board, and their launches.  The entries, their
+// FleetObs, FleetMotionObs for the predicted fleet call and FleetPlanObs for the
+// planned one), the kernels that fill the pose board and the plan board's side
+// 0, and their launches.  The entries, their
 // checks and the plain instantiations stay in mpc_rollout.hip (episodes_run,
 // episodes_fleet_run); why the two are compiled apart: mpc_episodes_obs_launch.h.
 // (the headers' plain, non-template kernels are mpc_rollout.hip's: one definition
@@ -49,6 +50,20 @@ void launch_episodes_fleet_predicted(hipStream_t st, int32_t integrator, const F
                                      mpc_episodes_progress_t* progress, int64_t* n_blocked) {
   dispatch_mode(integrator, [&](auto I, auto R) {
     k_episodes_run<I, R, FleetMotionObs<R>, FleetMotionArgs><<<n_robots, kBlock, 0, st>>>(
+        A, cfgs, robots, A.n_steps, 1, log, cap, progress, n_blocked);
+  });
+}
+
+void launch_fleet_plan_begin(hipStream_t st, const FleetPos* board, int n_robots, FleetPlan* plan) {
+  k_fleet_plan_begin<<<(n_robots + 255) / 256, 256, 0, st>>>(board, n_robots, plan);
+}
+
+void launch_episodes_fleet_planned(hipStream_t st, int32_t integrator, const FleetPlanArgs& A,
+                                   int n_robots, const mpc_episode_config_t* cfgs,
+                                   RobotState* robots, mpc_episode_log_t* log, int cap,
+                                   mpc_episodes_progress_t* progress, int64_t* n_blocked) {
+  dispatch_mode(integrator, [&](auto I, auto R) {
+    k_episodes_run<I, R, FleetPlanObs<R>, FleetPlanArgs><<<n_robots, kBlock, 0, st>>>(
         A, cfgs, robots, A.n_steps, 1, log, cap, progress, n_blocked);
   });
 }

@@ -503,10 +503,16 @@ int episodes_run(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacl
 // check_episodes_run; the count zeroed on the stream, then one launch per
 // fleet call, launch i on the board's side (call0 + i) & 1; neighbours_out
 // describes the last launch, so only that one gets it.
-// predicted (mpc_episodes_fleet_run_predicted): the motion board checked right
-// after the pose board, its side 0 zeroed on the stream before fleet call 0
-// (nobody has moved yet), and FleetMotionObs' launches on both boards' sides.
-int episodes_fleet_run(void* state, void* board, bool predicted, void* motion, int64_t call0,
+// kFleetMoved (mpc_episodes_fleet_run_predicted): `second`, the motion board,
+// checked right after the pose board, its side 0 zeroed on the stream before
+// fleet call 0 (nobody has moved yet), and FleetMotionObs' launches on both
+// boards' sides.  kFleetPlanned (mpc_episodes_fleet_run_planned): `second`, the
+// plan board, checked in the same place, its side 0 filled from the pose
+// board's before fleet call 0 (everybody stands), and FleetPlanObs' launches.
+enum FleetPrediction { kFleetStanding, kFleetMoved, kFleetPlanned };
+
+int episodes_fleet_run(void* state, void* board, FleetPrediction predict, void* second,
+                       int64_t call0,
                        const mpc_obstacle_t* obstacles, int32_t n_obstacles, double clearance,
                        double reach, int32_t n_robots,
                        int32_t n_steps, int32_t integrator, int32_t n_calls,
@@ -515,7 +521,7 @@ int episodes_fleet_run(void* state, void* board, bool predicted, void* motion, i
                        int32_t* neighbours_out, mpc_stream_t stream) {
   if (check_obstacles(obstacles, n_obstacles) != MPC_OK || !isfinite(clearance) ||
       !(clearance > 0) || !isfinite(reach) || reach < 0 || call0 < 0 || n_calls < 0 || !board ||
-      (predicted && !motion))
+      (predict != kFleetStanding && !second))
     return MPC_ERR_ARG;
   if (const int bad = check_episodes_run(state, n_robots, n_steps, integrator, n_calls, log,
                                          log_capacity))
@@ -532,18 +538,30 @@ int episodes_fleet_run(void* state, void* board, bool predicted, void* motion, i
   FleetPos* side[2] = {static_cast<FleetPos*>(board), static_cast<FleetPos*>(board) + n_robots};
   FleetArgs A{world_obstacles(obstacles, n_obstacles), nullptr, nullptr, clearance * clearance,
               reach * reach, n_obstacles, n_robots, nullptr};
-  FleetPos* moved[2] = {static_cast<FleetPos*>(motion),
-                        predicted ? static_cast<FleetPos*>(motion) + n_robots : nullptr};
-  if (predicted && call0 == 0 &&
-      hipMemsetAsync(moved[0], 0, static_cast<size_t>(n_robots) * sizeof(FleetPos), st) !=
-          hipSuccess)
-    return MPC_ERR_HIP;
+  FleetPos* moved[2] = {nullptr, nullptr};
+  FleetPlan* plans[2] = {nullptr, nullptr};
+  if (predict == kFleetMoved) {
+    moved[0] = static_cast<FleetPos*>(second);
+    moved[1] = moved[0] + n_robots;
+    if (call0 == 0 && hipMemsetAsync(moved[0], 0, static_cast<size_t>(n_robots) * sizeof(FleetPos),
+                                     st) != hipSuccess)
+      return MPC_ERR_HIP;
+  } else if (predict == kFleetPlanned) {
+    plans[0] = static_cast<FleetPlan*>(second);
+    plans[1] = plans[0] + n_robots;
+    if (call0 == 0) launch_fleet_plan_begin(st, side[0], n_robots, plans[0]);
+  }
   for (int32_t i = 0; i < n_calls; ++i) {
     const int at = static_cast<int>((call0 + i) & 1);
     A.board_in = side[at];
     A.board_out = side[at ^ 1];
     A.neighbours = i == n_calls - 1 ? neighbours_out : nullptr;
-    if (predicted)
+    if (predict == kFleetPlanned)
+      launch_episodes_fleet_planned(st, integrator, FleetPlanArgs{A, plans[at], plans[at ^ 1],
+                                                                  n_steps},
+                                    n_robots, dcfg, reinterpret_cast<RobotState*>(s), log,
+                                    log ? log_capacity : 0, progress, n_blocked_out);
+    else if (predict == kFleetMoved)
       launch_episodes_fleet_predicted(st, integrator, FleetMotionArgs{A, moved[at], moved[at ^ 1],
                                                                       n_steps},
                                       n_robots, dcfg, reinterpret_cast<RobotState*>(s), log,
@@ -1558,7 +1576,7 @@ int mpc_episodes_fleet_run(void* state, void* board, int64_t call0,
                            int32_t n_calls, mpc_episode_log_t* log, int32_t log_capacity,
                            mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
                            int32_t* neighbours_out, mpc_stream_t stream) {
-  return episodes_fleet_run(state, board, false, nullptr, call0, obstacles, n_obstacles, clearance,
+  return episodes_fleet_run(state, board, kFleetStanding, nullptr, call0, obstacles, n_obstacles, clearance,
                             reach, n_robots, n_steps, integrator, n_calls, log, log_capacity,
                             progress, n_blocked_out, neighbours_out, stream);
 }
@@ -1574,9 +1592,25 @@ int mpc_episodes_fleet_run_predicted(void* state, void* board, void* motion, int
                                      mpc_episode_log_t* log, int32_t log_capacity,
                                      mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
                                      int32_t* neighbours_out, mpc_stream_t stream) {
-  return episodes_fleet_run(state, board, true, motion, call0, obstacles, n_obstacles, clearance,
-                            reach, n_robots, n_steps, integrator, n_calls, log, log_capacity,
-                            progress, n_blocked_out, neighbours_out, stream);
+  return episodes_fleet_run(state, board, kFleetMoved, motion, call0, obstacles, n_obstacles,
+                            clearance, reach, n_robots, n_steps, integrator, n_calls, log,
+                            log_capacity, progress, n_blocked_out, neighbours_out, stream);
+}
+
+size_t mpc_episodes_fleet_plan_bytes(int32_t n_robots) {
+  return n_robots < 1 ? 0 : fleet_plan_bytes(n_robots);
+}
+
+int mpc_episodes_fleet_run_planned(void* state, void* board, void* plan, int64_t call0,
+                                   const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                                   double clearance, double reach, int32_t n_robots,
+                                   int32_t n_steps, int32_t integrator, int32_t n_calls,
+                                   mpc_episode_log_t* log, int32_t log_capacity,
+                                   mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
+                                   int32_t* neighbours_out, mpc_stream_t stream) {
+  return episodes_fleet_run(state, board, kFleetPlanned, plan, call0, obstacles, n_obstacles,
+                            clearance, reach, n_robots, n_steps, integrator, n_calls, log,
+                            log_capacity, progress, n_blocked_out, neighbours_out, stream);
 }
 
 // ----------------------------- full tree -----------------------------------

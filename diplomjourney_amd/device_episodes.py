@@ -76,7 +76,8 @@ class DeviceEpisodes(_RobotBatch):
     part of the state.  read_blocked(): per robot the candidates blocked in
     the steps of the last run().  With no circles run() is the call made
     without the feature.  Robots as each other's obstacles: DeviceFleet,
-    below (predict=True: their circles move with them).  Not provided: a table
+    below (predict=True: their circles move with them; predict="plan": along
+    their own plans).  Not provided: a table
     per robot, a radius per robot, circles in the full-tree episodes."""
 
     def __init__(self, engine, cfgs, n_steps=3, integrator="qk21", log_capacity=1024,
@@ -144,7 +145,10 @@ def fleet_reach(cfgs, n_steps, clearance, predict=False):
     distance or beyond has its circle out of every candidate's states.
     predict=True (DeviceFleet(predict=True)): 2 * far * (1 + 2**-40) +
     clearance — a neighbour's step-N circle lies up to one horizon's travel
-    from where the neighbour stands."""
+    from where the neighbour stands.  DeviceFleet(predict="plan") takes the
+    same reach: the two plan points a neighbour publishes are at most one
+    step's travel apart, so its step-N circle, a2 + (N - 2) * (a2 - a1), lies
+    within one horizon of the neighbour too."""
     far = max(int(n_steps) * c.delta_t * max(abs(c.v_max), abs(c.v_min)) for c in cfgs)
     if predict:
         return 2 * far * (1.0 + 2.0 ** -40) + float(clearance)
@@ -169,8 +173,18 @@ class DeviceFleet(DeviceEpisodes):
     or has not moved yet (fleet call 0), stands still.  The object then owns
     the motion board too (two sides of R {dx, dy}, the pose board's parity).
 
-    reach=None: fleet_reach(cfgs, n_steps, clearance, predict), the largest
-    distance a robot of the batch covers in one horizon (predict: two
+    predict="plan" (mpc_episodes_fleet_run_planned): each chosen neighbour's
+    circle follows the neighbour's own plan, the arc of its last winner.  Every
+    robot publishes two points (a1, a2) of it — the layers it means to reach
+    in the next call and the one after; a robot that has ended, took no step
+    or found no winner publishes its position twice — and a neighbour's circle
+    stands at a1 for step 1, at a2 for step 2 and at a2 + (j - 2) * (a2 - a1)
+    for step j >= 3.  The object then owns the plan board (`self.plan`: two
+    sides of R {x1, y1, x2, y2}, the pose board's parity); `self.motion` stays
+    None.  Any other value of predict raises ValueError.
+
+    reach=None: fleet_reach(cfgs, n_steps, clearance, bool(predict)), the
+    largest distance a robot of the batch covers in one horizon (predict: two
     horizons, the neighbour's travel too) plus clearance; a larger reach
     changes nothing, a smaller one ignores robots that could have mattered.
     The object owns the pose board, the count of fleet calls since reset()
@@ -178,20 +192,25 @@ class DeviceFleet(DeviceEpisodes):
     blocked over the fleet calls of the last run().  read_neighbours(): the
     last fleet call's (within reach before the cap, chosen robots in ascending
     (distance, index) order) per robot.
-    Not provided: any prediction but the constant displacement, per-robot
-    radii, per-robot static tables."""
+    Not provided: any prediction but the constant displacement and the two
+    plan points, per-robot radii, per-robot static tables."""
 
     def __init__(self, engine, cfgs, clearance, n_steps=3, integrator="qk21", log_capacity=1024,
                  obstacles=(), reach=None, predict=False):
         cfgs = list(cfgs)
         self.clearance = float(clearance)
-        self.predict = bool(predict)
-        self.reach = (fleet_reach(cfgs, n_steps, clearance, self.predict) if reach is None
+        if predict != "plan" and predict not in (True, False):
+            raise ValueError(f"predict is False, True or 'plan', not {predict!r}")
+        self.predict = predict if predict == "plan" else bool(predict)
+        self.reach = (fleet_reach(cfgs, n_steps, clearance, bool(self.predict)) if reach is None
                       else float(reach))
         n = len(cfgs)
         self.motion = (torch.zeros(native.lib().mpc_episodes_fleet_motion_bytes(n),
                                    dtype=torch.uint8, device=engine.device)
-                       if self.predict else None)
+                       if self.predict is True else None)
+        self.plan = (torch.zeros(native.lib().mpc_episodes_fleet_plan_bytes(n),
+                                 dtype=torch.uint8, device=engine.device)
+                     if self.predict == "plan" else None)
         self.board = torch.zeros(native.lib().mpc_episodes_fleet_board_bytes(n), dtype=torch.uint8,
                                  device=engine.device)
         self.neighbours = torch.full((n, 1 + MPC_MAX_OBSTACLES), -1, dtype=torch.int32,
@@ -216,7 +235,10 @@ class DeviceFleet(DeviceEpisodes):
                 self.n_steps, self._integ, n_calls, self.log.data_ptr(), self.log_capacity,
                 self.progress.data_ptr(), self.n_blocked.data_ptr(), self.neighbours.data_ptr(),
                 native.current_stream())
-        if self.predict:
+        if self.predict == "plan":
+            self._C.mpc_episodes_fleet_run_planned(self.state.data_ptr(), self.board.data_ptr(),
+                                                   self.plan.data_ptr(), *rest)
+        elif self.predict:
             self._C.mpc_episodes_fleet_run_predicted(self.state.data_ptr(), self.board.data_ptr(),
                                                      self.motion.data_ptr(), *rest)
         else:

@@ -149,6 +149,10 @@ PROTOTYPES = {
     "mpc_episodes_fleet_motion_bytes": (c_size_t, [_I32]),
     "mpc_episodes_fleet_run_predicted": (c_int, [_P, _P, _P, _I64, _P, _I32, _D, _D, _I32, _I32,
                                                  _I32, _I32, _P, _I32, _P, _P, _P, _P]),
+    # the planned fleet call: the plan board after the pose board
+    "mpc_episodes_fleet_plan_bytes": (c_size_t, [_I32]),
+    "mpc_episodes_fleet_run_planned": (c_int, [_P, _P, _P, _I64, _P, _I32, _D, _D, _I32, _I32,
+                                               _I32, _I32, _P, _I32, _P, _P, _P, _P]),
     "mpc_fulltree_episodes_state_bytes": (c_size_t, [_I32]),
     "mpc_fulltree_episodes_reset": (c_int, [_P, _I32, _P, _P]),
     "mpc_fulltree_episodes_run": (c_int, [_P, _I32, _P, _I32, _P, _I32, _D, _D, _D, _I32, _I32,

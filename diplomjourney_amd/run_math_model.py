@@ -486,11 +486,13 @@ def run_tree_fleet(starts, clearance, max_calls=None, integrator="qk21", engine=
     (on target, stuck, at max_calls) leaves its robot standing as an obstacle.
     `chunk` fleet calls per host call, the log read back once per host call.
     predict=True (mpc_episodes_fleet_run_predicted): a neighbour's circle
-    moves over the horizon with the neighbour's last displacement.
+    moves over the horizon with the neighbour's last displacement;
+    predict="plan" (mpc_episodes_fleet_run_planned): along the neighbour's own
+    plan, two points of its last winner's arc.
     reach=None: device_episodes.fleet_reach.  The return value and the stats
     keys are run_tree_batched's ("blocked" counts the robots' circles too).
-    Not provided: any prediction but the constant displacement, a radius or a
-    static table per robot, the full tree."""
+    Not provided: any prediction but the constant displacement and the two
+    plan points, a radius or a static table per robot, the full tree."""
     eng = engine or _device()[0]
     if obstacles is None:
         from . import math_model_tree as mmt

@@ -781,9 +781,63 @@ int mpc_episode_chain_error(const void* state, int32_t* error, mpc_stream_t stre
  *                        mpc_episodes_fleet_run's, in its order.  n_calls == 0
  *                        launches nothing and writes nothing (the motion board
  *                        is not zeroed either).
+ *   mpc_episodes_fleet_run_planned   a PLANNED FLEET CALL: a predicted fleet
+ *                        call in which each chosen neighbour's circle follows
+ *                        the neighbour's own plan (a constant-turn-rate
+ *                        prediction: the plan is the arc the neighbour means
+ *                        to drive).  Robot r's circles at horizon step j
+ *                        (j = 1..N) are the static ones, unmoved, and for each
+ *                        chosen neighbour q, with (a1, a2) = ((x1, y1),
+ *                        (x2, y2)) q's entry of this call's in side of the
+ *                        plan board, a circle of radius clearance centred at
+ *                        a1 for j = 1, at a2 for j = 2, and for j >= 3 at
+ *                        a2 + (double)(j - 2) * (a2 - a1) per coordinate (the
+ *                        difference one subtraction; the product rounded, then
+ *                        the sum).  The state after step j is tested against
+ *                        the step-j circles only (a flagged candidate's
+ *                        recomputed states likewise; rect+cum in the frame of
+ *                        the step's sums).  The selection (by the pose board's
+ *                        positions at the start of the call), reach, the cap,
+ *                        neighbours_out, n_blocked_out, the blocked / stale /
+ *                        NaN semantics and the lockstep by stream order are
+ *                        mpc_episodes_fleet_run's.
+ *                        plan: device memory of mpc_episodes_fleet_plan_bytes
+ *                        (two sides of R entries {double x1, y1, x2, y2}, 32 B
+ *                        each, with the pose board's parity: call c reads side
+ *                        c & 1 and writes the other), owned by the caller.
+ *                        Every block, stopped or not, writes its robot's entry
+ *                        of the out side — copies, no arithmetic.  A robot
+ *                        that took a step in this call, is still running after
+ *                        it, and whose step was not stale (its log record
+ *                        lacks MPC_EP_STALE) publishes two layers of its plan:
+ *                        with ot the winner's layer states 0..2 as its state
+ *                        holds them after the update (the last layer repeated
+ *                        for horizons below 3) and k the layer the update
+ *                        moved the robot to (0; 1 or 2 while it finishes: the
+ *                        finishing count m at the start of the call),
+ *                        (x1, y1) = ot[min(k + 1, 2)] and (x2, y2) =
+ *                        ot[min(k + 2, 2)].  Every other robot — one that
+ *                        ended in this call, had ended before it, took no step
+ *                        or made a stale step — publishes its position after
+ *                        the call twice, x1 = x2 = x and y1 = y2 = y: it
+ *                        stands.  With call0 == 0 the entry fills side 0 of
+ *                        the plan board on `stream` before its first launch,
+ *                        from the pose board's side 0, with (x, y, x, y), so
+ *                        fleet call 0 of a planned run is
+ *                        mpc_episodes_fleet_run's, bit for bit.  The pose
+ *                        board, its layout and _begin are unchanged.  The plan
+ *                        board is valid only for an unbroken sequence of
+ *                        planned calls since call0 = 0: mixing entries on one
+ *                        board is not supported and not checked.
+ *                        MPC_ERR_ARG before any HIP call: plan NULL (checked
+ *                        right after board); every other rejection is
+ *                        mpc_episodes_fleet_run's, in its order.  n_calls == 0
+ *                        launches nothing and writes nothing (the plan board
+ *                        is not filled either).
  * Not provided: per-robot static tables, per-robot radii (one clearance for
  * all), any prediction of the others' motion but the constant displacement of
- * _run_predicted, and the full-tree episodes (mpc_fulltree_episodes_*), which
+ * _run_predicted and the two plan points of _run_planned (the state stores
+ * three layers), and the full-tree episodes (mpc_fulltree_episodes_*), which
  * take no circles at all.
  * ------------------------------------------------------------------------- */
 typedef struct mpc_episodes_progress {
@@ -820,6 +874,14 @@ int mpc_episodes_fleet_run_predicted(void* state, void* board, void* motion, int
                                      mpc_episode_log_t* log, int32_t log_capacity,
                                      mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
                                      int32_t* neighbours_out, mpc_stream_t stream);
+size_t mpc_episodes_fleet_plan_bytes(int32_t n_robots);
+int mpc_episodes_fleet_run_planned(void* state, void* board, void* plan, int64_t call0,
+                                   const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                                   double clearance, double reach, int32_t n_robots,
+                                   int32_t n_steps, int32_t integrator, int32_t n_calls,
+                                   mpc_episode_log_t* log, int32_t log_capacity,
+                                   mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
+                                   int32_t* neighbours_out, mpc_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Full-tree MPC of run_math_model.py / math_model.py.

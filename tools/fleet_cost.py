@@ -34,6 +34,16 @@ hipMemsetAsync of the motion board's side 0 inside the event pair.  The
 formation's time per block comes from the stamps as the selection's does
 (tools/timeline.py fleet: formation_ns).
 
+The planned column (mpc_episodes_fleet_run_planned): planned_K is one planned
+fleet call for the same robots, alternated with fleet_K and predicted_K in the
+same process; planned_K - predicted_K is what the plan board costs over the
+motion board — a 32-B entry per neighbour instead of 16 B, staged in LDS, and
+a 32-B write.  It is made as the predicted column is: fleet call 2 on a board
+of standing plans (both sides every robot's position twice, so the work is the
+fleet call's); planned_4_call0 is fleet call 0, with the entry's fill of the
+plan board's side 0 inside the event pair.  plan_formation_ns comes from the
+stamps as formation_ns does.
+
     python tools/fleet_cost.py [--launches 40] [--out profiles/fleet/cost.json]
 Needs a GPU (no fallback)."""
 import argparse
@@ -102,12 +112,37 @@ def classes():
                 self.neighbours.data_ptr() if self.counted else None, native.current_stream())
             self.call0 += int(n_calls)
 
-    return Baseline, Fleet, Predicted
+    class Planned(Fleet):
+        call = 2        # (0: the entry fills the plan board's side 0 first)
+
+        def reset(self):
+            """... and a plan board on which everybody stands: both sides every
+            robot's (x, y, x, y), from the pose board's side 0 (untimed)."""
+            super().reset()
+            import torch
+            pos = self.board.view(torch.float64)[:2 * self.R].view(self.R, 2)
+            side = torch.cat([pos, pos], dim=1).reshape(-1)
+            self.plan.view(torch.float64).copy_(torch.cat([side, side]))
+
+        def run(self, n_calls):
+            self._C.mpc_episodes_fleet_run_planned(
+                self.state.data_ptr(), self.board.data_ptr(), self.plan.data_ptr(), self.call,
+                self._obs, self._n_obs, self.clearance, self.reach, self.R, self.n_steps,
+                self._integ, int(n_calls), self.log.data_ptr(), self.log_capacity,
+                self.progress.data_ptr(), self.n_blocked.data_ptr() if self.counted else None,
+                self.neighbours.data_ptr() if self.counted else None, native.current_stream())
+            self.call0 += int(n_calls)
+
+    return Baseline, Fleet, Predicted, Planned
 
 
 def measure(eng, integ, n, launches, warmup):
     import torch
-    Baseline, Fleet, Predicted = classes()
+    Baseline, Fleet, Predicted, Planned = classes()
+
+    def planned(k):
+        return Planned(eng, fleet_configs(n, k), CLEARANCE, 3, integ, log_capacity=1, reach=REACH,
+                       predict="plan")
     far = lambda k: cost_timing.circles(k, lambda i: (-100.0 - 0.1 * i, -100.0))
     objs, variants = {}, [("plain_a", None)]
     objs["plain_a"] = Baseline(eng, fleet_configs(n, 0), 3, integ, log_capacity=1)
@@ -118,15 +153,20 @@ def measure(eng, integ, n, launches, warmup):
         objs[f"fleet_{k}"] = Fleet(eng, cfgs, CLEARANCE, 3, integ, log_capacity=1, reach=REACH)
         objs[f"predicted_{k}"] = Predicted(eng, cfgs, CLEARANCE, 3, integ, log_capacity=1,
                                            reach=REACH, predict=True)
-        variants += [(f"obstacles_{k}", k), (f"fleet_{k}", k), (f"predicted_{k}", k)]
+        objs[f"planned_{k}"] = planned(k)
+        variants += [(f"obstacles_{k}", k), (f"fleet_{k}", k), (f"predicted_{k}", k),
+                     (f"planned_{k}", k)]
     objs["fleet_4_counted"] = Fleet(eng, fleet_configs(n, 4), CLEARANCE, 3, integ, log_capacity=1,
                                     reach=REACH)
     objs["fleet_4_counted"].counted = True
     objs["predicted_4_call0"] = Predicted(eng, fleet_configs(n, 4), CLEARANCE, 3, integ,
                                           log_capacity=1, reach=REACH, predict=True)
     objs["predicted_4_call0"].call = 0
+    objs["planned_4_call0"] = planned(4)
+    objs["planned_4_call0"].call = 0
     objs["plain_b"] = Baseline(eng, fleet_configs(n, 0), 3, integ, log_capacity=1)
-    variants += [("fleet_4_counted", 4), ("predicted_4_call0", 4), ("plain_b", None)]
+    variants += [("fleet_4_counted", 4), ("predicted_4_call0", 4), ("planned_4_call0", 4),
+                 ("plain_b", None)]
     variants = tuple(variants)
 
     # ~60 us of device work ahead of every timed launch: the host has enqueued the
@@ -169,6 +209,13 @@ def measure(eng, integ, n, launches, warmup):
         p["over_fleet_us"] = p["median_us"] - f["median_us"]
         p["over_fleet_share"] = p["over_fleet_us"] / f["median_us"]
         p["fleet_quartile_band_us"] = [f["p25_us"], f["p75_us"]]
+        q = rows[f"planned_{k}"]
+        q["over_fleet_us"] = q["median_us"] - f["median_us"]
+        q["over_fleet_share"] = q["over_fleet_us"] / f["median_us"]
+        q["over_predicted_us"] = q["median_us"] - p["median_us"]
+        q["predicted_quartile_band_us"] = [p["p25_us"], p["p75_us"]]
+        q["slower_than_predicted_by_more_than_its_spread"] = (
+            q["over_predicted_us"] > p["p75_us"] - p["p25_us"])
     return {"integrator": integ, "robots": n, "n_steps": 3, "rows": rows,
             "same_step_in_every_row": same, "plain_median_us": base,
             "plain_quartile_band_us": [min(a["p25_us"], b["p25_us"]),
@@ -177,15 +224,17 @@ def measure(eng, integ, n, launches, warmup):
 
 
 def stamped_ns(n, integ, k=0):
-    """The selection's time per block and the per-step tables' formation, from
-    the stamps: tools/timeline.py fleet N K in a process of its own (it loads
-    the variant library), its JSON line's selection_ns and formation_ns."""
+    """The selection's time per block and the per-step tables' formation
+    (predicted, planned), from the stamps: tools/timeline.py fleet N K in a
+    process of its own (it loads the variant library), its JSON line's
+    selection_ns, formation_ns and plan_formation_ns."""
     import subprocess
     out = subprocess.run([sys.executable, os.path.join(REPO, "tools", "timeline.py"), "fleet",
                           str(n), str(k), "--integ", integ], capture_output=True, text=True,
                          check=True).stdout
     line = json.loads([ln for ln in out.splitlines() if ln.startswith("JSON ")][-1][5:])
-    return float(line["selection_ns"]), float(line["formation_ns"])
+    return (float(line["selection_ns"]), float(line["formation_ns"]),
+            float(line["plan_formation_ns"]))
 
 
 def main():
@@ -209,8 +258,10 @@ def main():
             # the scan, measured where it runs: the selection's time per block from
             # the stamps (tools/timeline.py fleet, the variant library, a process of
             # its own), once per round of blocks (two blocks per CU at a time)
-            m["selection_ns_per_block"], m["formation_0_ns_per_block"] = stamped_ns(n, integ)
-            m["formation_13_ns_per_block"] = stamped_ns(n, integ, 13)[1]
+            (m["selection_ns_per_block"], m["formation_0_ns_per_block"],
+             m["plan_formation_0_ns_per_block"]) = stamped_ns(n, integ)
+            _, m["formation_13_ns_per_block"], m["plan_formation_13_ns_per_block"] = stamped_ns(
+                n, integ, 13)
             m["rounds_of_blocks"] = -(-n // (2 * cus))
             m["scan_us"] = m["selection_ns_per_block"] * m["rounds_of_blocks"] / 1e3
             m["formation_0_us"] = m["formation_0_ns_per_block"] * m["rounds_of_blocks"] / 1e3
@@ -235,6 +286,7 @@ def main():
               "zero inside band + scan", m["zero_inside_band_plus_scan"], "same step",
               m["same_step_in_every_row"], "formation per block (0 / 13 neighbours, ns)",
               m["formation_0_ns_per_block"], m["formation_13_ns_per_block"],
+              "planned", m["plan_formation_0_ns_per_block"], m["plan_formation_13_ns_per_block"],
               "predicted_0 inside the fleet band + formation",
               m["predicted_0_inside_fleet_band_plus_formation"])
         for name, r in m["rows"].items():
@@ -242,7 +294,9 @@ def main():
                      f"({100 * r['share_of_call']:.1f} % of the call)  neighbours "
                      f"{r['neighbours_min_max']}" if "share_of_call" in r else
                      f"  over the fleet call {r['over_fleet_us']:7.2f} us "
-                     f"({100 * r['over_fleet_share']:.1f} %)" if "over_fleet_us" in r else "")
+                     f"({100 * r['over_fleet_share']:.1f} %)"
+                     + (f"  over the predicted call {r['over_predicted_us']:7.2f} us"
+                        if "over_predicted_us" in r else "") if "over_fleet_us" in r else "")
             print(f"  {name:16s} median {r['median_us']:8.2f} us  p25 {r['p25_us']:8.2f}  "
                   f"p75 {r['p75_us']:8.2f}{extra}")
 

@@ -34,7 +34,10 @@ its `grid` phase less the plain one's is what the selection takes (the second
 unit's table: mpc_debug_timeline's which = 3).  A predicted fleet call
 (mpc_episodes_fleet_run_predicted, fleet call 0: every motion entry zero, the
 work the same) is stamped beside it: its `grid` phase less the fleet call's is
-the per-step tables' formation; the motion write follows the last stamp.
+the per-step tables' formation; the motion write follows the last stamp.  A
+planned fleet call (mpc_episodes_fleet_run_planned, fleet call 0: everybody's
+plan is to stand, the work the same) likewise: plan_formation_ns, and its phases
+less the predicted call's.
 run: the persistent run (k_episode_run), per step of the last launch (the
 fields: csrc/mpc_timeline.h)."""
 import argparse
@@ -198,7 +201,9 @@ def fleet(a):
                "fleet": (FLEET_TL, DeviceFleet(eng, cfgs, FC.CLEARANCE, 3, a.integ,
                                                log_capacity=1, reach=FC.REACH)),
                "predicted": (FLEET_TL, DeviceFleet(eng, cfgs, FC.CLEARANCE, 3, a.integ,
-                                                   log_capacity=1, reach=FC.REACH, predict=True))}
+                                                   log_capacity=1, reach=FC.REACH, predict=True)),
+               "planned": (FLEET_TL, DeviceFleet(eng, cfgs, FC.CLEARANCE, 3, a.integ,
+                                                 log_capacity=1, reach=FC.REACH, predict="plan"))}
     out = {}
     for name, (which, ep) in batches.items():
         mean = [0.0] * 6
@@ -217,7 +222,7 @@ def fleet(a):
         tot = sorted(sum(raw[8 * r:8 * r + 6]) * 10 for r in range(R))
         out[name + "_block_ns_p50_p99_max"] = [tot[len(tot) // 2], tot[(99 * len(tot)) // 100],
                                                tot[-1]]
-        print(f"{name:5s} " + "  ".join(f"{k} {v:.0f}" for k, v in out[name].items())
+        print(f"{name:9s} " + "  ".join(f"{k} {v:.0f}" for k, v in out[name].items())
               + f"  total {sum(mean):.0f} ns/call; blocks p50 / p99 / max "
               + " / ".join(str(t) for t in out[name + "_block_ns_p50_p99_max"]), flush=True)
     within = [w for w, _ in batches["fleet"][1].read_neighbours()]
@@ -232,6 +237,11 @@ def fleet(a):
     out["predicted_less_fleet_ns"] = {k: out["predicted"][k] - out["fleet"][k] for k in PH}
     print("predicted less fleet, per phase: "
           + "  ".join(f"{k} {v:.0f}" for k, v in out["predicted_less_fleet_ns"].items()))
+    # a planned call stages the neighbours' entries in LDS ahead of the same formation
+    out["plan_formation_ns"] = out["planned"]["grid"] - out["fleet"]["grid"]
+    out["planned_less_predicted_ns"] = {k: out["planned"][k] - out["predicted"][k] for k in PH}
+    print("planned less predicted, per phase: "
+          + "  ".join(f"{k} {v:.0f}" for k, v in out["planned_less_predicted_ns"].items()))
     print("JSON " + json.dumps({"robots": R, "neighbours": a.neighbours, "integ": a.integ, **out}))
 
 
