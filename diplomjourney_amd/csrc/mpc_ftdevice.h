@@ -81,4 +81,33 @@ MPC_HD __forceinline__ FtState ft_apply(const FtState& in, const FtCtl& u, const
   return o;
 }
 
+// Keep-out circles (mpc_fulltree_argmin_obstacles): a layer state (x, y) lies
+// strictly inside the circle (cx, cy, r2 = r * r) — the predicate of the
+// rollout's CircleObs (mpc_device.h), in world coordinates.  A NaN state is
+// inside nothing.
+MPC_HD __forceinline__ bool ft_inside(double x, double y, double cx, double cy, double r2) {
+  const double dx = x - cx, dy = y - cy;
+  return fma(dy, dy, dx * dx) < r2;
+}
+
+// Reach culling.  vh_max: the largest |v * h| of the control table (NaN entries
+// ignored; +inf if some |v * h| is).  One ft_apply moves a state by
+//   |d| <= |v h| (1 + e) + 2^-53 (|x'| + |y'|)
+// — the trig pair's norm and, for QK21, the quadrature's eleven roundings are
+// within e << 2^-20 of 1; the last term is the rounding of the new position
+// itself.  A leaf state inside circle (c, r) has |x'| <= |cx| + r, |y'| <= |cy| + r,
+// and ft_inside evaluates its squared distance to within 4 ulp.  So a layer-1
+// state whose leaf can be inside lies nearer to c than
+//   R = (r + vh_max (1 + 2^-20) + 2^-50 (|cx| + |cy| + r)) (1 + 2^-20),
+// the slack 2^-20 covering e, the roundings of R and of R * R, and those of the
+// test that compares against it.  Returns R * R: a layer-1 state with
+// d2 >= R * R (ft_inside's d2) has no leaf inside the circle.  +inf for an
+// infinite vh_max: nothing is culled.
+MPC_HD __forceinline__ double ft_reach_r2(double cx, double cy, double r2, double vh_max) {
+  constexpr double kSlack = 1.0 + 0x1p-20;
+  const double r = sqrt(r2);
+  const double R = (r + vh_max * kSlack + 0x1p-50 * (fabs(cx) + fabs(cy) + r)) * kSlack;
+  return R * R;
+}
+
 }  // namespace mpc

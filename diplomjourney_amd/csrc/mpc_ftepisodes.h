@@ -67,6 +67,7 @@ struct FtEpisode {
 // many controls (48 B each, 24 KiB: ftl_live_offset).
 constexpr int kFtEpMaxS1 = 512;
 
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ void k_ft_episodes_reset(const mpc_fulltree_episode_config_t* __restrict__ cfgs,
                                     int n, FtEpisode* __restrict__ eps) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -87,6 +88,7 @@ __global__ void k_ft_episodes_reset(const mpc_fulltree_episode_config_t* __restr
   E.max_calls = c.max_calls;
   eps[r] = E;
 }
+#endif
 
 // The call's launch-wide facts, written by k_ftl_prepare.
 struct FtLockstep {
@@ -323,6 +325,7 @@ __global__ __launch_bounds__(kBlock) void k_ftl_update(
         [threadIdx.x] = reinterpret_cast<const uint64_t*>(&s_log)[threadIdx.x];
 }
 
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ void k_ftl_progress(const FtEpisode* __restrict__ eps, int n,
                                mpc_episodes_progress_t* __restrict__ progress) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -331,5 +334,6 @@ __global__ void k_ftl_progress(const FtEpisode* __restrict__ eps, int n,
   progress[r].stop = eps[r].stop;
   progress[r].candidates = eps[r].leaves;
 }
+#endif
 
 }  // namespace mpc

@@ -73,6 +73,56 @@ __device__ __forceinline__ double ft_leaf(const FtState& l1, const FtCtl& u, con
   return cost_fulltree(lf.x, lf.y, lf.ph, F);
 }
 
+// Keep-out circles in the leaf loop (mpc_fulltree_argmin_obstacles; the style
+// of NoObs / CircleObs, mpc_device.h).  FtNoObs: the kernels without circles
+// (no obstacle statement is instantiated: their code is unchanged).
+// FtCircleObs: a leaf is blocked if any of its three layer states lies strictly
+// inside a circle (ft_inside, mpc_ftdevice.h).
+//   t        the world table, kernel argument 0 (scalar loads)
+//   reach2   per circle, the squared radius inflated by one last-layer step
+//            (ft_reach_r2, written by k_ft_reach): a layer-1 state at that
+//            squared distance or beyond has no leaf inside the circle
+//   n        circles in use
+//   blocked  the wave's count of blocked leaves (wave-uniform)
+struct FtNoObs {
+  static constexpr bool kOn = false;
+};
+struct FtCircleObs {
+  static constexpr bool kOn = true;
+  ObsTable t;
+  const double* __restrict__ reach2;
+  int n;
+  int64_t blocked = 0;
+
+  // (x, y) strictly inside any of the n circles
+  __device__ __forceinline__ bool inside_any(double x, double y) const {
+    bool in = false;
+    for (int i = 0; i < n; ++i) in |= ft_inside(x, y, t->c[i].cx, t->c[i].cy, t->c[i].r2);
+    return in;
+  }
+};
+
+// The waves' blocked-leaf counts (LDS only in the kernels that call this), in
+// two halves around block_argmin, whose barrier orders the stores before
+// thread 0's reads: one 64-bit atomic per block with a non-zero sum.
+__device__ __forceinline__ int64_t* ft_blocked_slots() {
+  __shared__ int64_t s_blocked[kWaves];
+  return s_blocked;
+}
+__device__ __forceinline__ void ft_store_blocked(int64_t wave_blocked) {
+  if ((threadIdx.x & 63) == 0) ft_blocked_slots()[threadIdx.x >> 6] = wave_blocked;
+}
+__device__ __forceinline__ void ft_add_blocked(int64_t* __restrict__ n_blocked) {
+  if (threadIdx.x == 0 && n_blocked) {
+    int64_t total = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) total += ft_blocked_slots()[w];
+    if (total)
+      atomicAdd(reinterpret_cast<unsigned long long*>(n_blocked),
+                static_cast<unsigned long long>(total));
+  }
+}
+
 // wave / n_waves: this wave's rank among the waves that share [u_lo, u_hi)
 // (the launch's waves; a block's own in the device-resident episodes).
 // Each lane keeps the first strict minimum of its leaves — which ascend in
@@ -89,12 +139,23 @@ __device__ __forceinline__ double ft_leaf(const FtState& l1, const FtCtl& u, con
 // Costs are compared as doubles: the criterion is >= 0, where the double order
 // is the cost keys' (+-0 equal, +inf and NaN never below a best; fmin ignores
 // a NaN), so the key is formed once per lane.
-template <int INTEG, bool ROT>
+// Obs::kOn (FtCircleObs), per piece:
+//   * layers 0 and 1 are tested once per lane, where l0 and l1 are formed; a
+//     lane whose pair is blocked counts its k2_hi - k2_lo leaves and gets a NaN
+//     l1.x — NaN leaves, which never win and are inside nothing, so the k2 loop
+//     needs no mask for it; a piece whose real lanes are all blocked is skipped;
+//   * reach culling: each lane tests its l1 against every circle inflated by
+//     one last-layer step (reach2); a ballot per circle gives the wave-uniform
+//     list of the circles that some lane can reach.  An empty list runs the
+//     plain k2 loops below; otherwise the hooked loops test the listed circles
+//     only, a blocked leaf's cost becoming +inf before the quad minimum;
+//   * the winning quad's re-evaluation applies the same mask (all circles).
+template <int INTEG, bool ROT, class Obs = FtNoObs>
 __device__ __forceinline__ void ft_leaves_body(const Consts& K, const FtCrit& F,
                                                const FtCtl* __restrict__ ctl, int64_t s1,
                                                int64_t u_lo, int64_t u_hi,
                                                uint64_t& best_k, int64_t& best_i, int64_t wave,
-                                               int64_t n_waves) {
+                                               int64_t n_waves, Obs* obs = nullptr) {
   const int lane = threadIdx.x & 63;
   const int64_t n_pairs = s1 * s1;
   const int64_t total = u_hi - u_lo, share = total / n_waves, rem = total % n_waves;
@@ -113,9 +174,54 @@ __device__ __forceinline__ void ft_leaves_body(const Consts& K, const FtCrit& F,
     const int64_t mm = m < n_pairs ? m : n_pairs - 1;
     const int64_t k0 = mm / s1, k1 = mm - k0 * s1;
     const FtState l0 = ft_apply<INTEG, ROT>(s0, ctl[k0], K);
-    const FtState l1 = ft_apply<INTEG, ROT>(l0, ctl[k1], K);
+    FtState l1 = ft_apply<INTEG, ROT>(l0, ctl[k1], K);
     int32_t q = -1;   // the piece's best quad (first k2; -1: none)
     int64_t k2 = k2_lo;
+    if constexpr (Obs::kOn) {
+      const bool real = m < n_pairs;   // (a clamped lane counts nothing)
+      bool pair_blocked = false;
+      uint32_t list = 0;               // the circles some lane's l1 can reach (wave-uniform)
+      for (int i = 0; i < obs->n; ++i) {
+        const double cx = obs->t->c[i].cx, cy = obs->t->c[i].cy, r2 = obs->t->c[i].r2;
+        const double dx = l1.x - cx, dy = l1.y - cy;
+        const double d2 = fma(dy, dy, dx * dx);   // (ft_inside's own operations)
+        pair_blocked |= ft_inside(l0.x, l0.y, cx, cy, r2) | (d2 < r2);
+        // (!(>=): a NaN l1 stays on the list — its leaves are NaN either way)
+        if (__ballot(!(d2 >= obs->reach2[i])) != 0) list |= 1u << i;
+      }
+      obs->blocked += __popcll(__ballot(real && pair_blocked)) * (k2_hi - k2_lo);
+      if (__ballot(real && !pair_blocked) == 0) continue;   // (wave-uniform; u has advanced)
+      if (pair_blocked) l1.x = __builtin_nan("");
+      if (list != 0) {   // the plain loops' twins, with the listed circles
+        for (; k2 < k2_hi;) {
+          const int nq = k2 + 4 <= k2_hi ? 4 : 1;   // (a quad, or a quad of one)
+          double c[4], x[4], y[4];
+          bool in[4] = {false, false, false, false};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const FtState lf = ft_apply<INTEG, ROT>(l1, ctl[j < nq ? k2 + j : k2], K);
+            c[j] = cost_fulltree(lf.x, lf.y, lf.ph, F);
+            x[j] = lf.x;
+            y[j] = lf.y;
+          }
+          for (uint32_t rest = list; rest != 0; rest &= rest - 1) {
+            const int i = __builtin_ctz(rest);
+            const double cx = obs->t->c[i].cx, cy = obs->t->c[i].cy, r2 = obs->t->c[i].r2;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) in[j] |= ft_inside(x[j], y[j], cx, cy, r2);
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (j < nq) obs->blocked += __popcll(__ballot(real && in[j]));
+            c[j] = in[j] ? __builtin_inf() : c[j];
+          }
+          const double cm = fmin(fmin(c[0], c[1]), fmin(c[2], c[3]));
+          if (cm < best_c) q = static_cast<int32_t>(k2);
+          best_c = fmin(best_c, cm);
+          k2 += nq;
+        }
+      }
+    }
     for (; k2 + 4 <= k2_hi; k2 += 4) {   // wave-uniform controls
       const double c0 = ft_leaf<INTEG, ROT>(l1, ctl[k2], K, F);
       const double c1 = ft_leaf<INTEG, ROT>(l1, ctl[k2 + 1], K, F);
@@ -143,8 +249,15 @@ __device__ __forceinline__ void ft_leaves_body(const Consts& K, const FtCrit& F,
       // (a quad of one — a piece's last leaves — matches at j = 0: the scan
       // never reaches past its quad)
       int32_t hit = -1;
-      for (int32_t j = 0; j < 4 && hit < 0 && best_q + j < s1; ++j)
-        if (ft_leaf<INTEG, ROT>(l1, ctl[best_q + j], K, F) == best_c) hit = best_q + j;
+      for (int32_t j = 0; j < 4 && hit < 0 && best_q + j < s1; ++j) {
+        if constexpr (Obs::kOn) {   // (a blocked leaf may share best_c's bits)
+          const FtState lf = ft_apply<INTEG, ROT>(l1, ctl[best_q + j], K);
+          if (cost_fulltree(lf.x, lf.y, lf.ph, F) == best_c && !obs->inside_any(lf.x, lf.y))
+            hit = best_q + j;
+        } else {
+          if (ft_leaf<INTEG, ROT>(l1, ctl[best_q + j], K, F) == best_c) hit = best_q + j;
+        }
+      }
       best_i = best_mm * s1 + (hit >= 0 ? hit : best_q);   // (hit >= 0: same bits)
     }
   }
@@ -233,6 +346,7 @@ struct FtRobot {
   double atan_t;
 };
 
+#ifndef MPC_TEMPLATES_ONLY   // (a unit that is not mpc_rollout.hip: mpc_episodes_obs_launch.h)
 __global__ void k_ft_robots(const mpc_fulltree_problem_t* __restrict__ probs, int n,
                             double L, double t_a, double t_b, FtRobot* __restrict__ robots) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -251,6 +365,7 @@ __global__ void k_ft_robots(const mpc_fulltree_problem_t* __restrict__ probs, in
   robots[r].K = consts_from_problem(q);
   robots[r].atan_t = probs[r].atan_target;
 }
+#endif
 
 template <int INTEG, bool ROT>
 __global__ __launch_bounds__(kBlock, kFtWaves) void k_ft_leaves_batched(

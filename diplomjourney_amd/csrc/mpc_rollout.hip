@@ -1637,10 +1637,28 @@ size_t mpc_fulltree_workspace_bytes(int32_t n_v, int32_t n_beta) {
   return ft_part_offset(static_cast<int64_t>(n_v) * n_beta) + kFtMaxBlocks * sizeof(Rec);
 }
 
-int mpc_fulltree_argmin(const mpc_fulltree_problem_t* p, const double* v_grid, int32_t n_v,
-                        const double* beta_grid, int32_t n_beta, double incumbent,
-                        int32_t integrator, int32_t shard, int32_t n_shards, void* ws,
-                        size_t ws_bytes, mpc_fulltree_result_t* out, mpc_stream_t stream) {
+// The circle entries' reach radii (k_ft_reach): MPC_MAX_OBSTACLES doubles in the
+// flag word's 256-byte slot.
+static constexpr size_t kFtReachOffset = 64;
+static_assert(kFtReachOffset + MPC_MAX_OBSTACLES * sizeof(double) <= 256, "the flag slot");
+
+// n_blocked_out of the full-tree circle entries: n counts, zeroed on the stream.
+static int ft_zero_blocked(int64_t* n_blocked_out, int32_t n, hipStream_t st) {
+  if (n_blocked_out && hipMemsetAsync(n_blocked_out, 0, static_cast<size_t>(n) * sizeof(int64_t),
+                                      st) != hipSuccess)
+    return MPC_ERR_HIP;
+  return MPC_OK;
+}
+
+// mpc_fulltree_argmin (no circles, no count) and mpc_fulltree_argmin_obstacles:
+// without circles the launches of the plain entry.
+static int fulltree_argmin(const mpc_fulltree_problem_t* p, const mpc_obstacle_t* obstacles,
+                           int32_t n_obstacles, const double* v_grid, int32_t n_v,
+                           const double* beta_grid, int32_t n_beta, double incumbent,
+                           int32_t integrator, int32_t shard, int32_t n_shards, void* ws,
+                           size_t ws_bytes, int64_t* n_blocked_out, mpc_fulltree_result_t* out,
+                           mpc_stream_t stream) {
+  if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
   if (!p || !v_grid || !beta_grid || !out || n_v < 1 || n_beta < 1) return MPC_ERR_ARG;
   if (n_shards < 1 || shard < 0 || shard >= n_shards) return MPC_ERR_ARG;
   const int64_t s1 = static_cast<int64_t>(n_v) * n_beta;
@@ -1654,6 +1672,7 @@ int mpc_fulltree_argmin(const mpc_fulltree_problem_t* p, const double* v_grid, i
   Rec* part = reinterpret_cast<Rec*>(w + ft_part_offset(s1));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (hipMemsetAsync(no_rot, 0, sizeof(uint32_t), st) != hipSuccess) return MPC_ERR_HIP;
+  if (ft_zero_blocked(n_blocked_out, 1, st) != MPC_OK) return MPC_ERR_HIP;
   // the shard's contiguous range of work units (ft_units), shared out evenly
   // over a grid of kFtWaves blocks per CU (one wave per SIMD each: every SIMD
   // holds the same number of equal shares), fewer for a small tree
@@ -1667,12 +1686,37 @@ int mpc_fulltree_argmin(const mpc_fulltree_problem_t* p, const double* v_grid, i
   dispatch_integ_rot(integrator, [&](auto I, auto R) {
     k_ft_controls<I><<<cdiv(s1, kBlock), kBlock, 0, st>>>(K, v_grid, beta_grid, n_beta, s1, ctl,
                                                           no_rot);
-    k_ft_leaves<I, R><<<grid, kBlock, 0, st>>>(K, p->atan_target, ctl, no_rot, s1, u_lo, u_hi,
-                                                part);
+    if (n_obstacles == 0)
+      k_ft_leaves<I, R><<<grid, kBlock, 0, st>>>(K, p->atan_target, ctl, no_rot, s1, u_lo, u_hi,
+                                                  part);
+    else
+      launch_ft_leaves_obs(st, integrator, world_obstacles(obstacles, n_obstacles), n_obstacles,
+                           K, p->atan_target, ctl, no_rot,
+                           reinterpret_cast<double*>(w + ft_flag_offset(s1) + kFtReachOffset), s1,
+                           u_lo, u_hi, grid, part, n_blocked_out);
     k_ft_finalize<I, R><<<1, kFinBlock, 0, st>>>(part, static_cast<int>(grid), K, ctl, no_rot,
                                                  s1, incumbent, out);
   });
   return last_hip_status();
+}
+
+int mpc_fulltree_argmin(const mpc_fulltree_problem_t* p, const double* v_grid, int32_t n_v,
+                        const double* beta_grid, int32_t n_beta, double incumbent,
+                        int32_t integrator, int32_t shard, int32_t n_shards, void* ws,
+                        size_t ws_bytes, mpc_fulltree_result_t* out, mpc_stream_t stream) {
+  return fulltree_argmin(p, nullptr, 0, v_grid, n_v, beta_grid, n_beta, incumbent, integrator,
+                         shard, n_shards, ws, ws_bytes, nullptr, out, stream);
+}
+
+int mpc_fulltree_argmin_obstacles(const mpc_fulltree_problem_t* p,
+                                  const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                                  const double* v_grid, int32_t n_v, const double* beta_grid,
+                                  int32_t n_beta, double incumbent, int32_t integrator,
+                                  int32_t shard, int32_t n_shards, void* ws, size_t ws_bytes,
+                                  int64_t* n_blocked_out, mpc_fulltree_result_t* out,
+                                  mpc_stream_t stream) {
+  return fulltree_argmin(p, obstacles, n_obstacles, v_grid, n_v, beta_grid, n_beta, incumbent,
+                         integrator, shard, n_shards, ws, ws_bytes, n_blocked_out, out, stream);
 }
 
 static int64_t ft_blocks_per_robot(int64_t s1, int32_t n) {
@@ -1688,12 +1732,16 @@ size_t mpc_fulltree_batched_workspace_bytes(int32_t n_problems, int32_t n_v, int
          static_cast<size_t>(n_problems) * ft_blocks_per_robot(s1, n_problems) * sizeof(Rec);
 }
 
-int mpc_fulltree_argmin_batched(const mpc_fulltree_problem_t* problems,
-                                const double* incumbents, int32_t n_problems, double L,
-                                double t_a, double t_b, const double* v_grid, int32_t n_v,
-                                const double* beta_grid, int32_t n_beta, int32_t integrator,
-                                void* ws, size_t ws_bytes, mpc_fulltree_result_t* out,
-                                mpc_stream_t stream) {
+// mpc_fulltree_argmin_batched and mpc_fulltree_argmin_batched_obstacles, in the
+// same way.
+static int fulltree_argmin_batched(const mpc_fulltree_problem_t* problems,
+                                   const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                                   const double* incumbents, int32_t n_problems, double L,
+                                   double t_a, double t_b, const double* v_grid, int32_t n_v,
+                                   const double* beta_grid, int32_t n_beta, int32_t integrator,
+                                   void* ws, size_t ws_bytes, int64_t* n_blocked_out,
+                                   mpc_fulltree_result_t* out, mpc_stream_t stream) {
+  if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
   if (!problems || !out || !v_grid || !beta_grid || n_problems < 1 || n_v < 1 || n_beta < 1 ||
       n_problems > 65535)
     return MPC_ERR_ARG;
@@ -1710,17 +1758,46 @@ int mpc_fulltree_argmin_batched(const mpc_fulltree_problem_t* problems,
   Rec* part = reinterpret_cast<Rec*>(w + ftb_part_offset(s1, n_problems));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (hipMemsetAsync(no_rot, 0, sizeof(uint32_t), st) != hipSuccess) return MPC_ERR_HIP;
+  if (ft_zero_blocked(n_blocked_out, n_problems, st) != MPC_OK) return MPC_ERR_HIP;
   const int64_t bx = ft_blocks_per_robot(s1, n_problems);
   k_ft_robots<<<cdiv(n_problems, 256), 256, 0, st>>>(problems, n_problems, L, t_a, t_b, robots);
   dispatch_integ_rot(integrator, [&](auto I, auto R) {
     k_ft_controls<I><<<cdiv(s1, kBlock), kBlock, 0, st>>>(Kw, v_grid, beta_grid, n_beta, s1,
                                                           ctl, no_rot);
-    k_ft_leaves_batched<I, R><<<dim3(static_cast<unsigned>(bx), n_problems), kBlock, 0, st>>>(
-        robots, ctl, no_rot, s1, part);
+    if (n_obstacles == 0)
+      k_ft_leaves_batched<I, R><<<dim3(static_cast<unsigned>(bx), n_problems), kBlock, 0, st>>>(
+          robots, ctl, no_rot, s1, part);
+    else
+      launch_ft_leaves_batched_obs(
+          st, integrator, world_obstacles(obstacles, n_obstacles), n_obstacles, robots, n_problems,
+          ctl, no_rot, reinterpret_cast<double*>(w + ft_flag_offset(s1) + kFtReachOffset), s1, bx,
+          part, n_blocked_out);
     k_ft_finalize_batched<I, R><<<n_problems, kBlock, 0, st>>>(
         part, static_cast<int>(bx), robots, ctl, no_rot, s1, incumbents, out);
   });
   return last_hip_status();
+}
+
+int mpc_fulltree_argmin_batched(const mpc_fulltree_problem_t* problems,
+                                const double* incumbents, int32_t n_problems, double L,
+                                double t_a, double t_b, const double* v_grid, int32_t n_v,
+                                const double* beta_grid, int32_t n_beta, int32_t integrator,
+                                void* ws, size_t ws_bytes, mpc_fulltree_result_t* out,
+                                mpc_stream_t stream) {
+  return fulltree_argmin_batched(problems, nullptr, 0, incumbents, n_problems, L, t_a, t_b, v_grid,
+                                 n_v, beta_grid, n_beta, integrator, ws, ws_bytes, nullptr, out,
+                                 stream);
+}
+
+int mpc_fulltree_argmin_batched_obstacles(
+    const mpc_fulltree_problem_t* problems, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+    const double* incumbents, int32_t n_problems, double L, double t_a, double t_b,
+    const double* v_grid, int32_t n_v, const double* beta_grid, int32_t n_beta,
+    int32_t integrator, void* ws, size_t ws_bytes, int64_t* n_blocked_out,
+    mpc_fulltree_result_t* out, mpc_stream_t stream) {
+  return fulltree_argmin_batched(problems, obstacles, n_obstacles, incumbents, n_problems, L, t_a,
+                                 t_b, v_grid, n_v, beta_grid, n_beta, integrator, ws, ws_bytes,
+                                 n_blocked_out, out, stream);
 }
 
 // ----------------------------- full-tree episodes ----------------------------
@@ -1749,19 +1826,28 @@ int mpc_fulltree_episodes_reset(const mpc_fulltree_episode_config_t* cfgs, int32
   return last_hip_status();
 }
 
-int mpc_fulltree_episodes_run(void* state, int32_t n_robots, const double* v_grid, int32_t n_v,
-                              const double* beta_grid, int32_t n_beta, double L, double delta_t,
-                              double eps, int32_t integrator, int32_t max_calls,
-                              mpc_episode_log_t* log, int32_t log_capacity,
-                              mpc_episodes_progress_t* progress, mpc_stream_t stream) {
+// mpc_fulltree_episodes_run and mpc_fulltree_episodes_run_obstacles, in the same
+// way: one table for every robot and every call of the launch sequence, the
+// reach radii (k_ft_reach, per call: the control table is the call's) in the
+// FtLockstep slot of the state.
+static_assert(kFtReachOffset >= sizeof(FtLockstep), "the lockstep slot");
+static int fulltree_episodes_run(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                                 int32_t n_robots, const double* v_grid, int32_t n_v,
+                                 const double* beta_grid, int32_t n_beta, double L, double delta_t,
+                                 double eps, int32_t integrator, int32_t max_calls,
+                                 mpc_episode_log_t* log, int32_t log_capacity,
+                                 mpc_episodes_progress_t* progress, int64_t* n_blocked_out,
+                                 mpc_stream_t stream) {
+  if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
   if (!state || !v_grid || !beta_grid || n_robots < 1 || n_robots > 65535 || n_v < 1 ||
       n_beta < 1 || max_calls < 0 || log_capacity < 0 || (log && log_capacity < 1) ||
       !(L > 0.0) || !(delta_t > 0.0))
     return MPC_ERR_ARG;
   if (static_cast<int64_t>(n_v) * n_beta > kFtEpMaxS1) return MPC_ERR_UNSUPPORTED;
   if (mode_ok(integrator, false) != MPC_OK) return MPC_ERR_UNSUPPORTED;
-  if (max_calls == 0) return MPC_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (ft_zero_blocked(n_blocked_out, n_robots, st) != MPC_OK) return MPC_ERR_HIP;
+  if (max_calls == 0) return MPC_OK;
   FtEpisode* E = reinterpret_cast<FtEpisode*>(state);
   const int cap = log ? log_capacity : 0;
   // load-balanced lockstep (mpc_ftepisodes.h): three launches per call over
@@ -1774,12 +1860,19 @@ int mpc_fulltree_episodes_run(void* state, int32_t n_robots, const double* v_gri
   auto* part = reinterpret_cast<Rec*>(s + ftl_part_offset(n_robots));
   const int64_t s1 = static_cast<int64_t>(n_v) * n_beta;
   const int grid = static_cast<int>(std::min<int64_t>(kFtlMaxGrid, device_cus() * kFtWaves));
+  const Obstacles W = world_obstacles(obstacles, n_obstacles);
   dispatch_integ_rot(integrator, [&](auto I, auto R) {
     for (int call = 0; call < max_calls; ++call) {
       k_ftl_prepare<I><<<1, kFtlPrepBlock, 0, st>>>(E, n_robots, v_grid, n_v, beta_grid, n_beta,
                                                      L, delta_t, eps, grid, ls, ctl, live,
                                                      robots);
-      k_ftl_leaves<I, R><<<grid, kBlock, 0, st>>>(ls, ctl, live, robots, s1, part);
+      if (n_obstacles == 0)
+        k_ftl_leaves<I, R><<<grid, kBlock, 0, st>>>(ls, ctl, live, robots, s1, part);
+      else
+        launch_ftl_leaves_obs(
+            st, integrator, W, n_obstacles, ls, ctl, live, robots,
+            reinterpret_cast<double*>(s + ftl_ls_offset(n_robots) + kFtReachOffset), s1, grid,
+            part, n_blocked_out);
       k_ftl_update<I, R><<<n_robots, kBlock, 0, st>>>(E, ls, ctl, live, robots, part, s1,
                                                       delta_t, log, cap);
     }
@@ -1788,6 +1881,29 @@ int mpc_fulltree_episodes_run(void* state, int32_t n_robots, const double* v_gri
     k_ftl_progress<<<static_cast<unsigned>(cdiv(n_robots, 256)), 256, 0, st>>>(E, n_robots,
                                                                                progress);
   return last_hip_status();
+}
+
+int mpc_fulltree_episodes_run(void* state, int32_t n_robots, const double* v_grid, int32_t n_v,
+                              const double* beta_grid, int32_t n_beta, double L, double delta_t,
+                              double eps, int32_t integrator, int32_t max_calls,
+                              mpc_episode_log_t* log, int32_t log_capacity,
+                              mpc_episodes_progress_t* progress, mpc_stream_t stream) {
+  return fulltree_episodes_run(state, nullptr, 0, n_robots, v_grid, n_v, beta_grid, n_beta, L,
+                               delta_t, eps, integrator, max_calls, log, log_capacity, progress,
+                               nullptr, stream);
+}
+
+int mpc_fulltree_episodes_run_obstacles(void* state, const mpc_obstacle_t* obstacles,
+                                        int32_t n_obstacles, int32_t n_robots,
+                                        const double* v_grid, int32_t n_v,
+                                        const double* beta_grid, int32_t n_beta, double L,
+                                        double delta_t, double eps, int32_t integrator,
+                                        int32_t max_calls, mpc_episode_log_t* log,
+                                        int32_t log_capacity, mpc_episodes_progress_t* progress,
+                                        int64_t* n_blocked_out, mpc_stream_t stream) {
+  return fulltree_episodes_run(state, obstacles, n_obstacles, n_robots, v_grid, n_v, beta_grid,
+                               n_beta, L, delta_t, eps, integrator, max_calls, log, log_capacity,
+                               progress, n_blocked_out, stream);
 }
 
 }  // extern "C"

@@ -78,7 +78,8 @@ class DeviceEpisodes(_RobotBatch):
     without the feature.  Robots as each other's obstacles: DeviceFleet,
     below (predict=True: their circles move with them; predict="plan": along
     their own plans).  Not provided: a table
-    per robot, a radius per robot, circles in the full-tree episodes."""
+    per robot, a radius per robot.  (The full-tree episodes take circles too:
+    DeviceFtEpisodes.)"""
 
     def __init__(self, engine, cfgs, n_steps=3, integrator="qk21", log_capacity=1024,
                  obstacles=()):
@@ -262,29 +263,63 @@ class DeviceFtEpisodes(_RobotBatch):
     call the robots still running are compacted and every one's S1^3 leaves
     are spread over the whole GPU (the load-balanced lockstep form).  cfgs:
     MpcFulltreeEpisodeConfig per robot; v_grid / beta_grid: the script's grids
-    as device tensors."""
+    as device tensors.
+
+    obstacles / set_obstacles(): keep-out circles (x, y, r) in world
+    coordinates, at most 16, ONE table for all robots and all calls of a
+    run() (mpc_fulltree_episodes_run_obstacles): a leaf with a layer state
+    strictly inside one never wins; a call whose leaves are all blocked has
+    no winner (the stale one is returned again; on a robot's first call the
+    episode stops with MPC_EP_NO_TRAJ).  A robot that starts inside a circle
+    can leave it.  read_blocked(): per robot the leaves blocked in the calls
+    of the last run().  With no circles run() is the call made without the
+    feature."""
 
     def __init__(self, engine, cfgs, v_grid, beta_grid, L, delta_t, eps, integrator="qk21",
-                 log_capacity=256):
+                 log_capacity=256, obstacles=()):
         self.cfgs = (MpcFulltreeEpisodeConfig * len(cfgs))(*cfgs)
         self.vg, self.bg = v_grid, beta_grid
         self.L, self.delta_t, self.eps = float(L), float(delta_t), float(eps)
         super().__init__(engine.device, len(cfgs), native.lib().mpc_fulltree_episodes_state_bytes,
                          integrator, log_capacity)
+        self.n_blocked = torch.zeros(self.R, dtype=torch.int64, device=engine.device)
+        self._obs, self._n_obs, self._counted = None, 0, False
+        self.set_obstacles(obstacles)
         self.reset()
 
     def reset(self):
         self._C.mpc_fulltree_episodes_reset(ctypes.byref(self.cfgs), self.R,
                                             self.state.data_ptr(), native.current_stream())
         self.progress.zero_()
+        self._counted = False        # (read_blocked(): zeros until the next run())
+
+    def set_obstacles(self, circles):
+        """The keep-out circles of the run() calls from now on."""
+        obs, n = make_obstacles(circles)
+        if n > MPC_MAX_OBSTACLES:
+            raise ValueError(f"at most {MPC_MAX_OBSTACLES} obstacles")
+        self._obs, self._n_obs = obs, n
+
+    def read_blocked(self):
+        """Per robot (numpy int64; syncs) the leaves that the circles blocked
+        in the calls of the last run() (zeros after a run() without circles)."""
+        if not self._counted:
+            return np.zeros(self.R, dtype=np.int64)
+        return self.n_blocked.cpu().numpy().copy()
 
     def run(self, max_calls):
         """Enqueue up to max_calls MPC calls of every still-running robot
         (three launches per call, each bounded by one call's S1^3 leaves per
         robot spread over the GPU: no launch approaches the compute-lockup
         timeout whatever S1 and max_calls are)."""
-        self._C.mpc_fulltree_episodes_run(
-            self.state.data_ptr(), self.R, self.vg.data_ptr(), self.vg.numel(),
-            self.bg.data_ptr(), self.bg.numel(), self.L, self.delta_t, self.eps, self._integ,
-            int(max_calls), self.log.data_ptr(), self.log_capacity, self.progress.data_ptr(),
-            native.current_stream())
+        args = (self.R, self.vg.data_ptr(), self.vg.numel(), self.bg.data_ptr(), self.bg.numel(),
+                self.L, self.delta_t, self.eps, self._integ, int(max_calls), self.log.data_ptr(),
+                self.log_capacity, self.progress.data_ptr())
+        self._counted = bool(self._n_obs)
+        if not self._n_obs:
+            self._C.mpc_fulltree_episodes_run(self.state.data_ptr(), *args,
+                                              native.current_stream())
+        else:
+            self._C.mpc_fulltree_episodes_run_obstacles(
+                self.state.data_ptr(), self._obs, self._n_obs, *args, self.n_blocked.data_ptr(),
+                native.current_stream())

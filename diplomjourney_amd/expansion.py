@@ -23,13 +23,15 @@ def _integ(name_or_id):
     return int(name_or_id)
 
 
-def _blocked_ptr(n_blocked):
-    """Device pointer of the optional blocked-candidate counter (one int64)."""
+def _blocked_ptr(n_blocked, n=1):
+    """Device pointer of the optional blocked counter (n int64: one, or one per
+    robot of a batched full-tree call)."""
     if n_blocked is None:
         return None
     if not (isinstance(n_blocked, torch.Tensor) and n_blocked.is_cuda
-            and n_blocked.dtype == torch.int64 and n_blocked.numel() == 1):
-        raise TypeError("n_blocked must be a CUDA(HIP) int64 tensor of one element")
+            and n_blocked.dtype == torch.int64 and n_blocked.numel() == n
+            and n_blocked.is_contiguous()):
+        raise TypeError(f"n_blocked must be a contiguous CUDA(HIP) int64 tensor of {n} element(s)")
     return n_blocked.data_ptr()
 
 
@@ -214,36 +216,60 @@ def soa_to_tiled(v, beta):
 
 
 def fulltree_argmin(engine, problem, v_grid, beta_grid, incumbent, integrator="qk21", shard=0,
-                    n_shards=1):
+                    n_shards=1, obstacles=None, n_blocked=None, out=None):
     """Full-tree MPC step (run_math_model.py:133-228): S1^3 leaves from the
     device grids v_grid [|V|], beta_grid [|B|] (fp64 tensors on the engine's
     device); this call evaluates leaf shard `shard` of `n_shards`.  Returns
-    the device result buffer (uint8[FT_RESULT_BYTES])."""
+    the device result buffer (uint8[FT_RESULT_BYTES]).
+    obstacles: optional sequence of keep-out circles (x, y, r): a leaf with a
+    layer state inside one never wins (mpc_fulltree_argmin_obstacles); every
+    shard of a step takes the same table.  n_blocked: optional int64 device
+    tensor [1] receiving the shard's blocked leaves.  Without either, the call
+    is mpc_fulltree_argmin."""
     lib, C = engine.lib, native.calls()
     nv, nb = v_grid.numel(), beta_grid.numel()
     ws = engine._workspace(lib.mpc_fulltree_workspace_bytes(nv, nb))
-    out = torch.empty(FT_RESULT_BYTES, dtype=torch.uint8, device=engine.device)
-    C.mpc_fulltree_argmin(ctypes.byref(problem), v_grid.data_ptr(), nv, beta_grid.data_ptr(), nb,
-                          float(incumbent), _integ(integrator), int(shard), int(n_shards),
-                          ws.data_ptr(), ws.numel(), out.data_ptr(), native.current_stream())
+    if out is None:
+        out = torch.empty(FT_RESULT_BYTES, dtype=torch.uint8, device=engine.device)
+    obs, n_obs = make_obstacles(obstacles)
+    args = (v_grid.data_ptr(), nv, beta_grid.data_ptr(), nb, float(incumbent), _integ(integrator),
+            int(shard), int(n_shards), ws.data_ptr(), ws.numel())
+    if n_obs or n_blocked is not None:
+        C.mpc_fulltree_argmin_obstacles(ctypes.byref(problem), obs, n_obs, *args,
+                                        _blocked_ptr(n_blocked), out.data_ptr(),
+                                        native.current_stream())
+    else:
+        C.mpc_fulltree_argmin(ctypes.byref(problem), *args, out.data_ptr(),
+                              native.current_stream())
     return out
 
 
 def fulltree_argmin_batched(engine, problems_dev, incumbents_dev, L, t_a, t_b, v_grid,
-                            beta_grid, integrator="qk21", out=None):
+                            beta_grid, integrator="qk21", out=None, obstacles=None,
+                            n_blocked=None):
     """R robots' full trees (one per run_math_model episode, lockstep):
     problems_dev uint8[R * sizeof(mpc_fulltree_problem_t)], incumbents_dev
-    float64[R]; returns the device results uint8[R * FT_RESULT_BYTES]."""
+    float64[R]; returns the device results uint8[R * FT_RESULT_BYTES].
+    obstacles: optional keep-out circles (x, y, r), ONE table for all robots
+    (mpc_fulltree_argmin_batched_obstacles); n_blocked: optional int64 device
+    tensor [R], per robot its blocked leaves.  Without either, the call is
+    mpc_fulltree_argmin_batched."""
     lib, C = engine.lib, native.calls()
     R = problems_dev.numel() // ctypes.sizeof(MpcFulltreeProblem)
     nv, nb = v_grid.numel(), beta_grid.numel()
     ws = engine._workspace(lib.mpc_fulltree_batched_workspace_bytes(R, nv, nb))
     if out is None:
         out = torch.empty(R * FT_RESULT_BYTES, dtype=torch.uint8, device=engine.device)
-    C.mpc_fulltree_argmin_batched(
-        problems_dev.data_ptr(), incumbents_dev.data_ptr(), R, float(L), float(t_a),
-        float(t_b), v_grid.data_ptr(), nv, beta_grid.data_ptr(), nb, _integ(integrator),
-        ws.data_ptr(), ws.numel(), out.data_ptr(), native.current_stream())
+    obs, n_obs = make_obstacles(obstacles)
+    args = (incumbents_dev.data_ptr(), R, float(L), float(t_a), float(t_b), v_grid.data_ptr(), nv,
+            beta_grid.data_ptr(), nb, _integ(integrator), ws.data_ptr(), ws.numel())
+    if n_obs or n_blocked is not None:
+        C.mpc_fulltree_argmin_batched_obstacles(problems_dev.data_ptr(), obs, n_obs, *args,
+                                                _blocked_ptr(n_blocked, R), out.data_ptr(),
+                                                native.current_stream())
+    else:
+        C.mpc_fulltree_argmin_batched(problems_dev.data_ptr(), *args, out.data_ptr(),
+                                      native.current_stream())
     return out
 
 

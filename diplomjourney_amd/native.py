@@ -157,6 +157,15 @@ PROTOTYPES = {
     "mpc_fulltree_episodes_reset": (c_int, [_P, _I32, _P, _P]),
     "mpc_fulltree_episodes_run": (c_int, [_P, _I32, _P, _I32, _P, _I32, _D, _D, _D, _I32, _I32,
                                           _P, _I32, _P, _P]),
+    # the full tree with keep-out circles: (circles, count) after the first
+    # argument, n_blocked_out before out (the episodes: before the stream)
+    "mpc_fulltree_argmin_obstacles": (c_int, [POINTER(MpcFulltreeProblem), _P, _I32, _P, _I32, _P,
+                                              _I32, _D, _I32, _I32, _I32, _P, c_size_t, _P, _P,
+                                              _P]),
+    "mpc_fulltree_argmin_batched_obstacles": (c_int, [_P, _P, _I32, _P, _I32, _D, _D, _D, _P, _I32,
+                                                      _P, _I32, _I32, _P, c_size_t, _P, _P, _P]),
+    "mpc_fulltree_episodes_run_obstacles": (c_int, [_P, _P, _I32, _I32, _P, _I32, _P, _I32, _D, _D,
+                                                    _D, _I32, _I32, _P, _I32, _P, _P, _P]),
 }
 
 # Every symbol include/mpc_rollout.h declares (checked by tests/test_abi.py).

@@ -129,11 +129,22 @@ def _device():
     return _engine, _grids_dev
 
 
+def _barriers():
+    """A copy of math_model_tree.barriers, the keep-out circles registered with
+    math_model_tree.add_barrier_circle, as they stand at the call."""
+    from . import math_model_tree as mmt
+    return list(mmt.barriers)
+
+
 def predictive_control(_initial_x, _initial_y, _initial_phi, _initial_velocity, _target_x,
                        _target_y):
     """:133-228 — one MPC step over the full tree; returns [x, y, phi, v, beta]
     of the best leaf's first layer.  (_initial_velocity, _target_* are unused
-    by the reference's expansion as well.)"""
+    by the reference's expansion as well.)  The circles of
+    math_model_tree.barriers are read at the call, as run_tree_episode's
+    predictive_control reads them: a leaf with a layer state inside one never
+    wins (mpc_fulltree_argmin_obstacles; every shard takes the same table).
+    With none registered the call is mpc_fulltree_argmin."""
     global optimal_trajectory, optimal_criterion, t
     t += delta_t                                                   # :156
     eng, (vg, bg) = _device()
@@ -141,13 +152,16 @@ def predictive_control(_initial_x, _initial_y, _initial_phi, _initial_velocity, 
                            float(x_t), float(y_t), float(x_0), float(y_0),
                            float(np.arctan(x_t / y_t)), float(L), float(t),
                            float(t + delta_t))
+    circles = _barriers()
     if _group is None:
-        r = fulltree_result(fulltree_argmin(eng, p, vg, bg, optimal_criterion, INTEGRATOR))
+        r = fulltree_result(fulltree_argmin(eng, p, vg, bg, optimal_criterion, INTEGRATOR,
+                                            obstacles=circles))
     else:
         import torch.distributed as dist
         from .distributed import gather_bytes, select_fulltree
         rank, world = dist.get_rank(_group), dist.get_world_size(_group)
-        local = fulltree_argmin(eng, p, vg, bg, optimal_criterion, INTEGRATOR, rank, world)
+        local = fulltree_argmin(eng, p, vg, bg, optimal_criterion, INTEGRATOR, rank, world,
+                                obstacles=circles)
         gathered = gather_bytes(local, _group)
         r = select_fulltree(gathered.cpu().numpy().tobytes(), optimal_criterion)
     if r.found:
@@ -234,7 +248,7 @@ class _Robot:
         return 10000 * dist_t + 10 * angle ** 2 + 100 * 1000 ** 2
 
 
-def run_batched(starts, max_calls=None, integrator=None, chunk=256, stats=None):
+def run_batched(starts, max_calls=None, integrator=None, chunk=256, stats=None, obstacles=None):
     """The script's episode loop (:231-280) for len(starts) episodes at once,
     device-resident (mpc_fulltree_episodes_run, csrc/mpc_ftepisodes.h): one
     robot per episode; per call the robots still running are compacted and
@@ -246,13 +260,21 @@ def run_batched(starts, max_calls=None, integrator=None, chunk=256, stats=None):
     the per-step log: pre = (x, y, phi, v, t, optimal_criterion) before the
     call, ret, optimal_criterion after it); raises the script's TypeError if an
     episode's first call finds no winner.  stats (optional dict) receives the
-    lockstep-equivalent steps (the longest episode's calls) and the leaves."""
+    lockstep-equivalent steps (the longest episode's calls), the leaves and, as
+    "blocked", those of them that a keep-out circle blocked.
+    obstacles: keep-out circles (x, y, r), one table for all robots (one map;
+    at most 16).  None takes a copy of math_model_tree.barriers at the call,
+    the list run_episode's predictive_control scores against, so that the
+    batched and the sequential driver agree; a sequence, () included,
+    overrides it."""
     robots = [_Robot(s) for s in starts]
     cap = min(chunk, max_calls) if max_calls else chunk
-    eps_dev = device_ft_episodes(starts, max_calls, integrator, cap, robots)
+    eps_dev = device_ft_episodes(starts, max_calls, integrator, cap, robots, obstacles)
     logs = [[] for _ in robots]
+    blocked = 0
     while True:
         eps_dev.run(cap)
+        blocked += int(eps_dev.read_blocked().sum())
         for r, lg in enumerate(eps_dev.read_logs(first_step=[len(x) for x in logs])):
             logs[r].extend(lg[["x", "y", "phi", "v", "beta", "cost"]].tolist())
         calls, stop, leaves = eps_dev.read_progress()
@@ -261,6 +283,7 @@ def run_batched(starts, max_calls=None, integrator=None, chunk=256, stats=None):
     if stats is not None:
         stats["steps"] = stats.get("steps", 0) + int(calls.max(initial=0))
         stats["leaves"] = stats.get("leaves", 0) + int(leaves.sum())
+        stats["blocked"] = stats.get("blocked", 0) + blocked
     out = []
     for r, lg, st in zip(robots, logs, stop):
         if st & MPC_EP_NO_TRAJ:
@@ -284,31 +307,44 @@ def _stop_name(stop_bits):
             "on_target" if stop_bits & MPC_EP_ARRIVED else "max_calls")
 
 
-def device_ft_episodes(starts, max_calls=None, integrator=None, log_capacity=256, robots=None):
+def device_ft_episodes(starts, max_calls=None, integrator=None, log_capacity=256, robots=None,
+                       obstacles=None):
     """The device state of len(starts) full-tree episodes (DeviceFtEpisodes)
     with the script's grids, constants and first incumbents: run_batched's
-    engine, also driven directly by bench.py's workload G."""
+    engine, also driven directly by bench.py's workload G.  obstacles: as in
+    run_batched (None: a copy of math_model_tree.barriers at the call)."""
     eng, (vg, bg) = _device()
+    if obstacles is None:
+        obstacles = _barriers()
     integ = INTEGRATOR if integrator is None else integrator
     robots = robots or [_Robot(s) for s in starts]
     cfgs = [MpcFulltreeEpisodeConfig(float(r.x_0), float(r.y_0), float(r.phi_0), float(r.x_t),
                                      float(r.y_t), r.atan_t, float(r.crit), int(max_calls or 0), 0)
             for r in robots]
     return DeviceFtEpisodes(eng, cfgs, vg, bg, float(L), float(delta_t), float(eps), integ,
-                            log_capacity=log_capacity)
+                            log_capacity=log_capacity, obstacles=obstacles)
 
 
-def run_batched_lockstep(starts, max_calls=None, integrator=None):
+def run_batched_lockstep(starts, max_calls=None, integrator=None, obstacles=None, stats=None):
     """The script's episode loop (:231-280) for len(starts) episodes at once:
     one robot per episode, all robots step in lockstep, and every MPC step of
     all still-running episodes is ONE batched full-tree launch
     (mpc_fulltree_argmin_batched) with the episode updates on the host (round
     3's driver, kept as the device-resident run_batched's cross-check).  Each
     robot keeps its own never-reset incumbent, stale winner and stop rule.
-    Returns [(records, stop)] per episode, as run_episode does."""
+    Returns [(records, stop)] per episode, as run_episode does.
+    obstacles: as in run_batched (mpc_fulltree_argmin_batched_obstacles, one
+    table for all robots; None: a copy of math_model_tree.barriers at the
+    call).  stats (optional dict): "blocked" receives, per robot (a list), the
+    sum of its calls' blocked leaves, up to the call that raised if one did."""
     eng, (vg, bg) = _device()
     integ = INTEGRATOR if integrator is None else integrator
+    if obstacles is None:
+        obstacles = _barriers()
     robots = [_Robot(s) for s in starts]
+    blocked = [0] * len(robots)
+    if stats is not None:
+        stats["blocked"] = blocked
     step = 0
     while True:
         live = []
@@ -330,8 +366,14 @@ def run_batched_lockstep(starts, max_calls=None, integrator=None):
                                t_now, t_now + delta_t) for r in live])
         pd = torch.frombuffer(bytearray(bytes(probs)), dtype=torch.uint8).to(eng.device)
         inc = torch.tensor([r.crit for r in live], dtype=torch.float64, device=eng.device)
+        counts = (torch.zeros(len(live), dtype=torch.int64, device=eng.device)
+                  if len(obstacles) else None)
         res = fulltree_results(fulltree_argmin_batched(eng, pd, inc, L, t_now, t_now + delta_t,
-                                                       vg, bg, integ))
+                                                       vg, bg, integ, obstacles=obstacles,
+                                                       n_blocked=counts))
+        if counts is not None:
+            for r, n in zip(live, counts.tolist()):
+                blocked[robots.index(r)] += n
         for r, w in zip(live, res):
             pre = (r.x, r.y, r.phi, r.v, r.t, r.crit)
             r.t = t_now
@@ -427,8 +469,8 @@ def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, sta
     the list run_tree_episode's predictive_control scores against, so that
     the batched and the sequential driver agree; a sequence, () included,
     overrides it.  Robots as each other's obstacles: run_tree_fleet.  Not
-    provided: a table per robot, a radius per robot, circles in the full tree
-    (run_batched)."""
+    provided: a table per robot, a radius per robot.  (The full tree takes
+    circles too: run_batched.)"""
     eng = engine or _device()[0]
     if obstacles is None:
         from . import math_model_tree as mmt

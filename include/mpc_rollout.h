@@ -187,7 +187,9 @@ int mpc_rollout_finalize(const mpc_problem_t* p, const double* v_sc, const doubl
  * takes circles through mpc_episode_partials_obstacles, _step_obstacles and
  * _chain_step_obstacles, the batched robots' episodes through
  * mpc_episodes_run_obstacles (both below, where what still takes none is
- * listed); the batched one-shot entry and the full tree take no obstacles.
+ * listed), the full tree through mpc_fulltree_argmin_obstacles,
+ * _argmin_batched_obstacles and mpc_fulltree_episodes_run_obstacles (below);
+ * the batched one-shot entry takes no obstacles.
  */
 #define MPC_MAX_OBSTACLES 16
 typedef struct mpc_obstacle {
@@ -432,10 +434,10 @@ int mpc_episode_chain_step(const mpc_episode_config_t* cfg, void* state, int32_t
  * kernels, the same bytes.  EpisodeState and the block records are unchanged,
  * so finalize, the update and the multi-GPU expand / advance step follow as
  * they are.  Without obstacles: the fused step (mpc_episode_rollout), the
- * generated step, the persistent run, the exchange and P2P chained steps,
- * the batched one-shot entry (mpc_rollout_argmin_batched) and the full tree
- * with its episodes.  (The batched robots' episodes take circles through
- * mpc_episodes_run_obstacles.) */
+ * generated step, the persistent run, the exchange and P2P chained steps and
+ * the batched one-shot entry (mpc_rollout_argmin_batched).  (The batched
+ * robots' episodes take circles through mpc_episodes_run_obstacles, the full
+ * tree and its episodes through the mpc_fulltree_*_obstacles entries.) */
 int mpc_episode_partials_obstacles(void* state, const mpc_obstacle_t* obstacles,
                                    int32_t n_obstacles, const double* v_sc,
                                    const double* beta_sc, int64_t n_cand, int32_t n_steps,
@@ -837,8 +839,8 @@ int mpc_episode_chain_error(const void* state, int32_t* error, mpc_stream_t stre
  * Not provided: per-robot static tables, per-robot radii (one clearance for
  * all), any prediction of the others' motion but the constant displacement of
  * _run_predicted and the two plan points of _run_planned (the state stores
- * three layers), and the full-tree episodes (mpc_fulltree_episodes_*), which
- * take no circles at all.
+ * three layers), and robots as each other's circles in the full-tree episodes
+ * (mpc_fulltree_episodes_run_obstacles takes the static table only).
  * ------------------------------------------------------------------------- */
 typedef struct mpc_episodes_progress {
   int32_t calls;         /* MPC steps run so far                                     */
@@ -938,6 +940,49 @@ int mpc_fulltree_argmin_batched(const mpc_fulltree_problem_t* problems,
                                 void* ws, size_t ws_bytes, mpc_fulltree_result_t* out,
                                 mpc_stream_t stream);
 
+/* Keep-out circles in the full tree: the semantics of
+ * mpc_rollout_partials_obstacles, applied to leaves.
+ *   - A leaf (k0, k1, k2) is BLOCKED if any of its three layer states lies
+ *     strictly inside any circle, (x - cx)^2 + (y - cy)^2 < r^2 in world
+ *     coordinates (evaluated as fma(dy, dy, dx * dx) < r * r).  The start pose
+ *     is not tested (a robot that starts inside can leave).  A NaN state is
+ *     inside nothing.
+ *   - A blocked leaf never wins.  A shard, tree or robot whose leaves are all
+ *     blocked or non-finite reports what it reports for "no finite leaf": leaf
+ *     -1, found 0, cost +inf.
+ *   - Ties, the incumbent test, shard / n_shards, the result struct and the
+ *     workspace sizes are the plain entries', so the selection over shards and
+ *     the multi-GPU gather follow unchanged.
+ *   - n_obstacles == 0 launches the plain entry's kernels: the same result
+ *     byte for byte.
+ *   obstacles      host array of n_obstacles circles, read during the call only;
+ *                  ONE table for all robots of a batched call, and for all
+ *                  robots and all calls of an episodes launch sequence
+ *   n_blocked_out  optional device int64 (zeroed and written on `stream`), NULL
+ *                  skips it: the number of blocked leaves among the leaves this
+ *                  call owns — a (k0, k1) pair blocked at layer 0 or 1 counts
+ *                  every one of its leaves in the shard's work units, so the
+ *                  shards' counts of any n_shards sum to the tree's.
+ *                  _batched: [n_problems], per robot.  _episodes_run: [n_robots],
+ *                  per robot the sum over the calls of this launch sequence (as
+ *                  mpc_episodes_run_obstacles counts)
+ * MPC_ERR_ARG, before any HIP call: n_obstacles outside [0, MPC_MAX_OBSTACLES],
+ * obstacles NULL with n_obstacles > 0, a non-finite centre, r not finite or
+ * r <= 0.  The other arguments are the plain entries'. */
+int mpc_fulltree_argmin_obstacles(const mpc_fulltree_problem_t* p,
+                                  const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                                  const double* v_grid, int32_t n_v, const double* beta_grid,
+                                  int32_t n_beta, double incumbent, int32_t integrator,
+                                  int32_t shard, int32_t n_shards, void* ws, size_t ws_bytes,
+                                  int64_t* n_blocked_out, mpc_fulltree_result_t* out,
+                                  mpc_stream_t stream);
+int mpc_fulltree_argmin_batched_obstacles(
+    const mpc_fulltree_problem_t* problems, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+    const double* incumbents, int32_t n_problems, double L, double t_a, double t_b,
+    const double* v_grid, int32_t n_v, const double* beta_grid, int32_t n_beta,
+    int32_t integrator, void* ws, size_t ws_bytes, int64_t* n_blocked_out,
+    mpc_fulltree_result_t* out, mpc_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * Full-tree episodes, device-resident: run_math_model.py's
  * episode loop (:231-280) with its OWN full-tree MPC step (:133-228, the tree
@@ -963,6 +1008,10 @@ int mpc_fulltree_argmin_batched(const mpc_fulltree_problem_t* problems,
  *                                {calls, stop, leaves scored} per robot
  * A robot whose first call finds no winning leaf stops with MPC_EP_NO_TRAJ (the
  * script raises TypeError there: optimal_trajectory is still [0]).
+ *   mpc_fulltree_episodes_run_obstacles  the same with keep-out circles (above):
+ *                                a robot that starts inside a circle can leave
+ *                                it; one walled in from its first call stops
+ *                                with MPC_EP_NO_TRAJ
  * ------------------------------------------------------------------------- */
 #define MPC_EP_NO_TRAJ 64
 typedef struct mpc_fulltree_episode_config {
@@ -981,6 +1030,14 @@ int mpc_fulltree_episodes_run(void* state, int32_t n_robots, const double* v_gri
                               double eps, int32_t integrator, int32_t max_calls,
                               mpc_episode_log_t* log, int32_t log_capacity,
                               mpc_episodes_progress_t* progress, mpc_stream_t stream);
+int mpc_fulltree_episodes_run_obstacles(void* state, const mpc_obstacle_t* obstacles,
+                                        int32_t n_obstacles, int32_t n_robots,
+                                        const double* v_grid, int32_t n_v,
+                                        const double* beta_grid, int32_t n_beta, double L,
+                                        double delta_t, double eps, int32_t integrator,
+                                        int32_t max_calls, mpc_episode_log_t* log,
+                                        int32_t log_capacity, mpc_episodes_progress_t* progress,
+                                        int64_t* n_blocked_out, mpc_stream_t stream);
 
 #ifdef __cplusplus
 }
