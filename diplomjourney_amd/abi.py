@@ -5,6 +5,7 @@ oracle binding agree on the byte layout.  Layout is checked against the C
 compiler's sizeof/offsetof in tests/test_abi.py.
 """
 import ctypes
+import math
 
 MPC_MAX_STEPS = 32
 
@@ -65,6 +66,74 @@ def make_obstacles(obstacles):
     if not obs:
         return None, 0
     return (MpcObstacle * len(obs))(*[MpcObstacle(*o) for o in obs]), len(obs)
+
+
+MPC_MAX_POLYGONS = 4
+MPC_MAX_POLYGON_VERTICES = 8
+
+
+class MpcPolygon(ctypes.Structure):
+    """mpc_polygon_t: one convex keep-out polygon in world coordinates."""
+    _fields_ = [("n_vertices", ctypes.c_int32), ("reserved_", ctypes.c_int32),
+                ("x", ctypes.c_double * MPC_MAX_POLYGON_VERTICES),
+                ("y", ctypes.c_double * MPC_MAX_POLYGON_VERTICES)]
+
+
+def polygon_vertices(vertices):
+    """A polygon's vertices as a tuple of (x, y) floats.  The reference's closed
+    form — the first vertex repeated at the end — loses the repeat.  ValueError
+    for a vertex that is not (x, y) and for fewer than 3 or more than
+    MPC_MAX_POLYGON_VERTICES vertices."""
+    pts = [tuple(float(q) for q in p) for p in vertices]
+    if any(len(p) != 2 for p in pts):
+        raise ValueError("a polygon vertex is (x, y)")
+    if len(pts) > 1 and pts[0] == pts[-1]:
+        pts = pts[:-1]
+    if not 3 <= len(pts) <= MPC_MAX_POLYGON_VERTICES:
+        raise ValueError(f"a polygon has 3 to {MPC_MAX_POLYGON_VERTICES} vertices")
+    return tuple(pts)
+
+
+def polygon_is_convex(vertices):
+    """The entries' rule (include/mpc_rollout.h) on a polygon_vertices() tuple:
+    after normalising the orientation by the sign of the shoelace area, every
+    vertex other than an edge's two endpoints lies strictly on the inner side of
+    that edge's line."""
+    n = len(vertices)
+    if not all(math.isfinite(q) for p in vertices for q in p):
+        return False
+    x0, y0 = vertices[0]
+    area2 = 0.0
+    for i in range(1, n - 1):
+        (xa, ya), (xb, yb) = vertices[i], vertices[i + 1]
+        area2 += (xa - x0) * (yb - y0) - (xb - x0) * (ya - y0)
+    if not math.isfinite(area2) or area2 == 0.0:
+        return False
+    sgn = 1.0 if area2 > 0 else -1.0
+    for i in range(n):
+        j = (i + 1) % n
+        dx, dy = vertices[j][0] - vertices[i][0], vertices[j][1] - vertices[i][1]
+        for k in range(n):
+            if k in (i, j):
+                continue
+            if not sgn * (dx * (vertices[k][1] - vertices[i][1])
+                          - dy * (vertices[k][0] - vertices[i][0])) > 0.0:
+                return False
+    return True
+
+
+def make_polygons(polygons):
+    """(MpcPolygon array or None, count) of a sequence of vertex lists
+    (polygon_vertices: each a sequence of (x, y), closed or not)."""
+    polys = [polygon_vertices(g) for g in (polygons or ())]
+    if not polys:
+        return None, 0
+    arr = (MpcPolygon * len(polys))()
+    for rec, pts in zip(arr, polys):
+        rec.n_vertices = len(pts)
+        for i, (px, py) in enumerate(pts):
+            rec.x[i], rec.y[i] = px, py
+    return arr, len(polys)
 
 
 class MpcResult(ctypes.Structure):

@@ -9,6 +9,8 @@
 //                      (kernarg_obs); blocked_slots, store_wave_blocked,
 //                      add_block_blocked: the blocked-count epilogue, also of
 //                      the episode kernels (mpc_chain.h, mpc_episode_obs.h).
+//   k_rollout_argmin_keepout / _stream_keepout   the same with keep-out circles
+//                      and polygons (kernarg_keepout, mpc_keepout.h).
 //   k_stream_probe     the streaming kernel's memory side alone.
 //   k_rollout_argmin_batched / k_finalize_batched   robot-segmented variant.
 //   select_index, k_select_winner   lexicographic min over gathered per-rank results.
@@ -25,6 +27,7 @@
 #include "../../include/mpc_rollout.h"
 #include "mpc_argmin.h"
 #include "mpc_device.h"
+#include "mpc_keepout.h"
 #include "mpc_lanes.h"
 #include "mpc_winner.h"
 
@@ -152,6 +155,41 @@ __global__ __launch_bounds__(kBlock, kObsStreamWaves) void k_rollout_argmin_stre
     unsigned long long* __restrict__ n_blocked) {
   rollout_argmin_body<kCplWide, INTEG, ROT, false, false>(Karg, nullptr, v, b, n_cand, n_steps,
                                                            part, nullptr, kernarg_obs<NOBS>(),
+                                                           n_blocked);
+}
+
+// The keep-out variants (mpc_rollout_partials_keepout): the twins of the two
+// kernels above with the KeepoutObs<NOBS> hook (mpc_keepout.h) — the same
+// bodies, grids, launch bounds and blocked-count epilogue.  The circle and
+// polygon tables and the polygon count are the FIRST argument `O`, read
+// through the segment pointer as above.
+template <int NOBS>
+__device__ __forceinline__ KeepoutObs<NOBS> kernarg_keepout() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const auto* a = (const __attribute__((address_space(4))) KeepoutArgs*)
+      __builtin_amdgcn_kernarg_segment_ptr();
+  return KeepoutObs<NOBS>{&a->loop, &a->world, &a->ploop, &a->pworld, a->n_polygons};
+#else
+  return KeepoutObs<NOBS>{nullptr, nullptr, nullptr, nullptr, 0};   // (host pass: parse only)
+#endif
+}
+
+template <int CPL, int INTEG, int ROT, bool STATES, int NOBS>
+__global__ __launch_bounds__(kBlock, 1) void k_rollout_argmin_keepout(
+    KeepoutArgs O, Consts Karg, const double* __restrict__ v, const double* __restrict__ b,
+    int64_t n_cand, int n_steps, Rec* __restrict__ part, double* __restrict__ states,
+    unsigned long long* __restrict__ n_blocked) {
+  rollout_argmin_body<CPL, INTEG, ROT, STATES, false>(Karg, nullptr, v, b, n_cand, n_steps, part,
+                                                       states, kernarg_keepout<NOBS>(), n_blocked);
+}
+
+template <int INTEG, int ROT, int NOBS>
+__global__ __launch_bounds__(kBlock, kObsStreamWaves) void k_rollout_argmin_stream_keepout(
+    KeepoutArgs O, Consts Karg, const double* __restrict__ v, const double* __restrict__ b,
+    int64_t n_cand, int n_steps, Rec* __restrict__ part,
+    unsigned long long* __restrict__ n_blocked) {
+  rollout_argmin_body<kCplWide, INTEG, ROT, false, false>(Karg, nullptr, v, b, n_cand, n_steps,
+                                                           part, nullptr, kernarg_keepout<NOBS>(),
                                                            n_blocked);
 }
 

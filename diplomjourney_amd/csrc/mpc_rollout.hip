@@ -37,6 +37,7 @@
 #include "mpc_fulltree.h"
 #include "mpc_generated.h"
 #include "mpc_host_consts.h"
+#include "mpc_keepout.h"
 #include "mpc_kernels.h"
 #include "mpc_lanes.h"
 #include "mpc_run.h"
@@ -248,6 +249,35 @@ void launch_rollout_obs(hipStream_t st, int32_t integrator, const Consts& K, con
         k_rollout_argmin_stream_obs<I, R, NOBS><<<g2, kBlock, 0, st>>>(O, K, v, b, n_cand, n_steps,
                                                                        part, n_blocked);
       });
+  });
+}
+
+// The keep-out variant of launch_rollout_obs (circles and polygons,
+// mpc_keepout.h): the same grid and path choice.  The polygon count is a
+// launch argument (a loop in the hook); the circle count an instantiation: on
+// the streaming path 0 (polygons alone) or all 16, on the
+// one-candidate-per-lane paths 16 (unused circles are padded, never entered).
+void launch_rollout_keepout(hipStream_t st, int32_t integrator, const Consts& K,
+                            const KeepoutArgs& O, int n_obs, const double* v, const double* b,
+                            int64_t n_cand, int n_steps, Rec* part, double* states,
+                            unsigned long long* n_blocked) {
+  const bool wide = !states && wide_ok(v, b, n_cand);
+  dispatch_mode(integrator, [&](auto I, auto R) {
+    constexpr int kAll = MPC_MAX_OBSTACLES;
+    const dim3 g1(static_cast<unsigned>(rollout_grid<1>(n_cand)));
+    const dim3 g2(static_cast<unsigned>(rollout_grid<kCplWide>(n_cand)));
+    if (states)
+      k_rollout_argmin_keepout<1, I, R, true, kAll><<<g1, kBlock, 0, st>>>(
+          O, K, v, b, n_cand, n_steps, part, states, n_blocked);
+    else if (!wide)
+      k_rollout_argmin_keepout<1, I, R, false, kAll><<<g1, kBlock, 0, st>>>(
+          O, K, v, b, n_cand, n_steps, part, nullptr, n_blocked);
+    else if (n_obs > 0)
+      k_rollout_argmin_stream_keepout<I, R, kAll><<<g2, kBlock, 0, st>>>(
+          O, K, v, b, n_cand, n_steps, part, n_blocked);
+    else
+      k_rollout_argmin_stream_keepout<I, R, 0><<<g2, kBlock, 0, st>>>(
+          O, K, v, b, n_cand, n_steps, part, n_blocked);
   });
 }
 
@@ -692,6 +722,52 @@ int mpc_rollout_argmin_obstacles(const mpc_problem_t* p, const mpc_obstacle_t* o
   const int a = mpc_rollout_partials_obstacles(p, obstacles, n_obstacles, v_sc, beta_sc, n_cand,
                                                n_steps, integrator, states_out, ws, ws_bytes,
                                                n_blocked_out, stream);
+  if (a != MPC_OK) return a;
+  return mpc_rollout_finalize(p, v_sc, beta_sc, n_cand, n_steps, index_base, incumbent,
+                              integrator, states_out != nullptr, ws, ws_bytes, out, stream);
+}
+
+int mpc_rollout_partials_keepout(const mpc_problem_t* p, const mpc_obstacle_t* obstacles,
+                                 int32_t n_obstacles, const mpc_polygon_t* polygons,
+                                 int32_t n_polygons, const double* v_sc, const double* beta_sc,
+                                 int64_t n_cand, int32_t n_steps, int32_t integrator,
+                                 double* states_out, void* ws, size_t ws_bytes,
+                                 int64_t* n_blocked_out, mpc_stream_t stream) {
+  const int a = check_args(p, v_sc, beta_sc, n_cand, n_steps, integrator, ws, ws_bytes);
+  if (a != MPC_OK) return a;
+  const int o = check_obstacles(obstacles, n_obstacles);
+  if (o != MPC_OK) return o;
+  const int g = check_polygons(polygons, n_polygons);
+  if (g != MPC_OK) return g;
+  if (n_polygons == 0)   // the circle entry (with no circles either: the plain kernels)
+    return mpc_rollout_partials_obstacles(p, obstacles, n_obstacles, v_sc, beta_sc, n_cand,
+                                          n_steps, integrator, states_out, ws, ws_bytes,
+                                          n_blocked_out, stream);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (n_blocked_out &&
+      hipMemsetAsync(n_blocked_out, 0, sizeof(*n_blocked_out), st) != hipSuccess)
+    return MPC_ERR_HIP;
+  const Consts K = host_consts(*p);
+  const bool cum = is_cum(integrator);
+  const KeepoutArgs O =
+      keepout_args(K, host_obstacles(K, obstacles, n_obstacles, cum), polygons, n_polygons, cum);
+  launch_rollout_keepout(st, integrator, K, O, n_obstacles, v_sc, beta_sc, n_cand, n_steps,
+                         static_cast<Rec*>(ws), states_out,
+                         reinterpret_cast<unsigned long long*>(n_blocked_out));
+  return last_hip_status();
+}
+
+int mpc_rollout_argmin_keepout(const mpc_problem_t* p, const mpc_obstacle_t* obstacles,
+                               int32_t n_obstacles, const mpc_polygon_t* polygons,
+                               int32_t n_polygons, const double* v_sc, const double* beta_sc,
+                               int64_t n_cand, int32_t n_steps, int64_t index_base,
+                               double incumbent, int32_t integrator, double* states_out, void* ws,
+                               size_t ws_bytes, int64_t* n_blocked_out, mpc_result_t* out,
+                               mpc_stream_t stream) {
+  if (!out || index_base < 0) return MPC_ERR_ARG;
+  const int a = mpc_rollout_partials_keepout(p, obstacles, n_obstacles, polygons, n_polygons, v_sc,
+                                             beta_sc, n_cand, n_steps, integrator, states_out, ws,
+                                             ws_bytes, n_blocked_out, stream);
   if (a != MPC_OK) return a;
   return mpc_rollout_finalize(p, v_sc, beta_sc, n_cand, n_steps, index_base, incumbent,
                               integrator, states_out != nullptr, ws, ws_bytes, out, stream);

@@ -28,7 +28,7 @@ import torch
 
 from . import math_model_tree as mmt
 from .abi import (MPC_EP_ARRIVED, MPC_EP_BREAK, MPC_EP_EVENT, MPC_EP_LIMIT, MPC_EP_STALE,
-                  MPC_EP_STUCK, make_problem)
+                  MPC_EP_STUCK, make_problem, polygon_vertices)
 from .device_episode import DeviceEpisode  # noqa: F401
 from .device_episodes import DeviceEpisodes, DeviceFleet, DeviceFtEpisodes  # noqa: F401
 from .distributed import exchange_winner, shard_range
@@ -50,11 +50,13 @@ def criterion0(x_t, y_t, x_0, y_0):
 class Episode:
     def __init__(self, engine, n_cand_total, n_steps, rank=0, world=1, seed=20261015,
                  integrator="rect", group=None, start=(0.0, 0.0, 0.0, 0.0, 0.0), target=(2, 3),
-                 max_steps=0, obstacles=()):
+                 max_steps=0, obstacles=(), polygons=()):
         self.eng = engine
         self.max_steps = int(max_steps)
         # keep-out circles (x, y, r): candidates that enter one never win
         self.obstacles = [tuple(o) for o in obstacles]
+        # convex keep-out polygons, each a sequence of (x, y): likewise
+        self.polygons = [polygon_vertices(g) for g in polygons]
         # module globals of the reference that outlive an episode: the last
         # winner's layer states, result_v, result_beta (None: the initial
         # [[[0]]], which has no layer states)
@@ -120,7 +122,8 @@ class Episode:
             events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         if events:
             events[0].record()
-        self.eng.partials(prob, self.v_sc, self.b_sc, self.integrator, obstacles=self.obstacles)
+        self.eng.partials(prob, self.v_sc, self.b_sc, self.integrator, obstacles=self.obstacles,
+                          polygons=self.polygons)
         if events:
             events[1].record()
         out = self.eng.finalize(prob, self.v_sc, self.b_sc, index_base=self.lo,

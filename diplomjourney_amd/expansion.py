@@ -14,7 +14,7 @@ import torch
 from . import native
 from .abi import (FT_RESULT_BYTES, INTEGRATORS, MPC_MAX_STEPS, MPC_TILE, PROBLEM_BYTES,
                   RESULT_BYTES, MpcFulltreeProblem, MpcFulltreeResult, MpcProblem, MpcResult,
-                  make_obstacles, result_from_bytes)
+                  make_obstacles, make_polygons, result_from_bytes)
 
 
 def _integ(name_or_id):
@@ -66,11 +66,16 @@ class Expansion:
         return self._ws
 
     # -- single problem --------------------------------------------------------
-    def _one_shot(self, name, problem, obstacles, n_blocked, args, tail):
+    def _one_shot(self, name, problem, obstacles, n_blocked, args, tail, polygons=None):
         """Entry `name`, or with obstacles / n_blocked its `_obstacles` twin: the
-        circles after the problem, n_blocked_out before `tail`."""
+        circles after the problem, n_blocked_out before `tail`; with polygons
+        its `_keepout` twin: the polygons after the circles."""
         obs, n_obs = make_obstacles(obstacles)
-        if n_obs or n_blocked is not None:
+        poly, n_poly = make_polygons(polygons)
+        if n_poly:
+            getattr(self._C, name + "_keepout")(ctypes.byref(problem), obs, n_obs, poly, n_poly,
+                                                *args, _blocked_ptr(n_blocked), *tail)
+        elif n_obs or n_blocked is not None:
             getattr(self._C, name + "_obstacles")(ctypes.byref(problem), obs, n_obs, *args,
                                                   _blocked_ptr(n_blocked), *tail)
         else:
@@ -78,7 +83,7 @@ class Expansion:
 
     def rollout_argmin(self, problem: MpcProblem, v_sc, beta_sc, index_base=0,
                        incumbent=math.inf, integrator="qk21", states=None, out=None,
-                       obstacles=None, n_blocked=None):
+                       obstacles=None, n_blocked=None, polygons=None):
         """Enqueue the expansion of one problem; returns the device result buffer.
 
         states: optional float64 tensor [n_steps, 3, n_cand] receiving every
@@ -87,7 +92,11 @@ class Expansion:
         whose state after any step lies inside one never wins
         (mpc_rollout_argmin_obstacles).  n_blocked: optional int64 device
         tensor [1] receiving the number of such candidates.  Without either,
-        the call is mpc_rollout_argmin.
+        the call is mpc_rollout_argmin.  polygons: optional sequence of convex
+        keep-out polygons, each a sequence of 3 to 8 vertices (x, y), closed or
+        not: a candidate whose state after any step lies strictly inside one
+        never wins either, and n_blocked counts both (mpc_rollout_argmin_keepout).
+        Without polygons the call is the one made without the argument.
         """
         _check_soa(v_sc, "v_sc")
         n_steps, n_cand = v_sc.shape
@@ -105,18 +114,19 @@ class Expansion:
                        (v_sc.data_ptr(), beta_sc.data_ptr(), n_cand, n_steps, int(index_base),
                         float(incumbent), _integ(integrator),
                         states.data_ptr() if states is not None else None, ws.data_ptr(),
-                        ws.numel()), (out.data_ptr(), native.current_stream()))
+                        ws.numel()), (out.data_ptr(), native.current_stream()), polygons)
         return out
 
     def partials(self, problem: MpcProblem, v_sc, beta_sc, integrator="qk21", obstacles=None,
-                 n_blocked=None):
+                 n_blocked=None, polygons=None):
         """Phase 1 only: the streaming rollout kernel (block arg-min records).
-        obstacles / n_blocked: as in rollout_argmin (mpc_rollout_partials_obstacles)."""
+        obstacles / n_blocked: as in rollout_argmin (mpc_rollout_partials_obstacles);
+        polygons: as there (mpc_rollout_partials_keepout)."""
         n_steps, n_cand = v_sc.shape
         ws = self._workspace(self.lib.mpc_workspace_bytes(n_cand, n_steps))
         self._one_shot("mpc_rollout_partials", problem, obstacles, n_blocked,
                        (v_sc.data_ptr(), beta_sc.data_ptr(), n_cand, n_steps, _integ(integrator),
-                        None, ws.data_ptr(), ws.numel()), (native.current_stream(),))
+                        None, ws.data_ptr(), ws.numel()), (native.current_stream(),), polygons)
 
     def finalize(self, problem: MpcProblem, v_sc, beta_sc, index_base=0, incumbent=math.inf,
                  integrator="qk21", out=None):

@@ -63,6 +63,12 @@ radius_u_turn = L / math.sin(beta_max)
 # The reference draws a "barrier_polygon" and reads it nowhere; this list is
 # what predictive_control scores against.  Empty: the reference's behaviour.
 barriers = []
+# Convex keep-out polygons, each a tuple of (x, y) vertices (add_barrier_polygon):
+# a candidate whose state after any layer lies strictly inside one never wins
+# either (mpc_rollout_argmin_keepout).  predictive_control and run_tree_episode
+# score against both lists; every other entry that reads `barriers` by default
+# takes circles only and refuses to run while this list is non-empty.
+barrier_polygons = []
 
 _engine = None
 
@@ -88,8 +94,34 @@ def add_barrier_circle(x, y, r):
     barriers.append((float(x), float(y), float(r)))
 
 
+def add_barrier_polygon(vertices):
+    """Keep candidates out of a convex polygon: `vertices` is a sequence of 3
+    to 8 (x, y) in either orientation, closed (the reference's
+    add_plot_polygon form, first vertex repeated at the end) or not.  Inflate
+    it for the robot's size and the distance driven in one step: only layer
+    states are tested, not the path between them.  ValueError for a polygon
+    that is not strictly convex and simple."""
+    from .abi import polygon_is_convex, polygon_vertices
+    pts = polygon_vertices(vertices)
+    if not polygon_is_convex(pts):
+        raise ValueError("a keep-out polygon is strictly convex and simple: split a non-convex "
+                         "or degenerate polygon into convex pieces")
+    barrier_polygons.append(pts)
+
+
+def require_no_barrier_polygons(who):
+    """For the entries that read `barriers` by default and take circles only:
+    ValueError while polygons are registered, so that none of them drives
+    through a registered barrier in silence."""
+    if barrier_polygons:
+        raise ValueError(f"{who} takes keep-out circles only, and math_model_tree.barrier_polygons "
+                         f"holds {len(barrier_polygons)} polygon(s): pass obstacles=... explicitly, "
+                         "or clear_barriers()")
+
+
 def clear_barriers():
     del barriers[:]
+    del barrier_polygons[:]
 
 
 def reset_state():
@@ -325,10 +357,10 @@ def predictive_control(_initial_x, _initial_y, _initial_phi, _target_x, _target_
         v_sc, b_sc = candidate_controls(V, list(_vector_beta), prediction_horizon, eng.device)
         problem = make_problem(_initial_x, _initial_y, _initial_phi, x_t, y_t, x_0, y_0, L,
                                t, t + delta_t)
-        if barriers:
+        if barriers or barrier_polygons:
             eng.rollout_argmin(problem, v_sc, b_sc, incumbent=optimal_criterion,
                                integrator=INTEGRATOR, states=global_coordinates.states,
-                               obstacles=barriers)
+                               obstacles=barriers, polygons=barrier_polygons)
         else:
             eng.rollout_argmin(problem, v_sc, b_sc, incumbent=optimal_criterion,
                                integrator=INTEGRATOR, states=global_coordinates.states)

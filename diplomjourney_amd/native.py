@@ -56,6 +56,11 @@ PROTOTYPES = {
                                                c_size_t, _P, _P]),
     "mpc_rollout_argmin_obstacles": (c_int, [_PROB, _P, _I32, _P, _P, _I64, _I32, _I64, _D, _I32,
                                              _P, _P, c_size_t, _P, _P, _P]),
+    # ... with keep-out polygons: (polygons, count) after the circles
+    "mpc_rollout_partials_keepout": (c_int, [_PROB, _P, _I32, _P, _I32, _P, _P, _I64, _I32, _I32,
+                                             _P, _P, c_size_t, _P, _P]),
+    "mpc_rollout_argmin_keepout": (c_int, [_PROB, _P, _I32, _P, _I32, _P, _P, _I64, _I32, _I64, _D,
+                                           _I32, _P, _P, c_size_t, _P, _P, _P]),
     "mpc_batched_workspace_bytes": (c_size_t, [_I32, _I64, _I32]),
     "mpc_rollout_argmin_batched": (c_int, [_P, _P, _I32, _P, _P, _I64, _I32, _I32, _P, c_size_t,
                                            _P, _P]),

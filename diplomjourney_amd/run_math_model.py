@@ -129,10 +129,13 @@ def _device():
     return _engine, _grids_dev
 
 
-def _barriers():
+def _barriers(who):
     """A copy of math_model_tree.barriers, the keep-out circles registered with
-    math_model_tree.add_barrier_circle, as they stand at the call."""
+    math_model_tree.add_barrier_circle, as they stand at the call.  `who` takes
+    circles only: ValueError while math_model_tree.barrier_polygons holds a
+    polygon (add_barrier_polygon), which it would drive through."""
     from . import math_model_tree as mmt
+    mmt.require_no_barrier_polygons(who)
     return list(mmt.barriers)
 
 
@@ -144,15 +147,16 @@ def predictive_control(_initial_x, _initial_y, _initial_phi, _initial_velocity, 
     math_model_tree.barriers are read at the call, as run_tree_episode's
     predictive_control reads them: a leaf with a layer state inside one never
     wins (mpc_fulltree_argmin_obstacles; every shard takes the same table).
-    With none registered the call is mpc_fulltree_argmin."""
+    With none registered the call is mpc_fulltree_argmin.  The full tree takes
+    no polygons: ValueError while math_model_tree.barrier_polygons holds one."""
     global optimal_trajectory, optimal_criterion, t
+    circles = _barriers("run_math_model.predictive_control")
     t += delta_t                                                   # :156
     eng, (vg, bg) = _device()
     p = MpcFulltreeProblem(float(_initial_x), float(_initial_y), float(_initial_phi),
                            float(x_t), float(y_t), float(x_0), float(y_0),
                            float(np.arctan(x_t / y_t)), float(L), float(t),
                            float(t + delta_t))
-    circles = _barriers()
     if _group is None:
         r = fulltree_result(fulltree_argmin(eng, p, vg, bg, optimal_criterion, INTEGRATOR,
                                             obstacles=circles))
@@ -313,9 +317,9 @@ def device_ft_episodes(starts, max_calls=None, integrator=None, log_capacity=256
     with the script's grids, constants and first incumbents: run_batched's
     engine, also driven directly by bench.py's workload G.  obstacles: as in
     run_batched (None: a copy of math_model_tree.barriers at the call)."""
-    eng, (vg, bg) = _device()
     if obstacles is None:
-        obstacles = _barriers()
+        obstacles = _barriers("device_ft_episodes / run_batched")
+    eng, (vg, bg) = _device()
     integ = INTEGRATOR if integrator is None else integrator
     robots = robots or [_Robot(s) for s in starts]
     cfgs = [MpcFulltreeEpisodeConfig(float(r.x_0), float(r.y_0), float(r.phi_0), float(r.x_t),
@@ -337,10 +341,10 @@ def run_batched_lockstep(starts, max_calls=None, integrator=None, obstacles=None
     table for all robots; None: a copy of math_model_tree.barriers at the
     call).  stats (optional dict): "blocked" receives, per robot (a list), the
     sum of its calls' blocked leaves, up to the call that raised if one did."""
+    if obstacles is None:
+        obstacles = _barriers("run_batched_lockstep")
     eng, (vg, bg) = _device()
     integ = INTEGRATOR if integrator is None else integrator
-    if obstacles is None:
-        obstacles = _barriers()
     robots = [_Robot(s) for s in starts]
     blocked = [0] * len(robots)
     if stats is not None:
@@ -471,10 +475,9 @@ def run_tree_batched(starts, max_calls=None, integrator="qk21", engine=None, sta
     overrides it.  Robots as each other's obstacles: run_tree_fleet.  Not
     provided: a table per robot, a radius per robot.  (The full tree takes
     circles too: run_batched.)"""
-    eng = engine or _device()[0]
     if obstacles is None:
-        from . import math_model_tree as mmt
-        obstacles = list(mmt.barriers)
+        obstacles = _barriers("run_tree_batched")
+    eng = engine or _device()[0]
     if max_calls == 0:
         return [([], "on_target" if is_on_target(s[0], s[1], s[3], s[4]) else "max_calls")
                 for s in starts]
@@ -535,10 +538,9 @@ def run_tree_fleet(starts, clearance, max_calls=None, integrator="qk21", engine=
     keys are run_tree_batched's ("blocked" counts the robots' circles too).
     Not provided: any prediction but the constant displacement and the two
     plan points, a radius or a static table per robot, the full tree."""
-    eng = engine or _device()[0]
     if obstacles is None:
-        from . import math_model_tree as mmt
-        obstacles = list(mmt.barriers)
+        obstacles = _barriers("run_tree_fleet")
+    eng = engine or _device()[0]
     if max_calls == 0:
         return [([], "on_target" if is_on_target(s[0], s[1], s[3], s[4]) else "max_calls")
                 for s in starts]

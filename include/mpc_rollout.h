@@ -208,6 +208,84 @@ int mpc_rollout_argmin_obstacles(const mpc_problem_t* p, const mpc_obstacle_t* o
                                  void* ws, size_t ws_bytes, int64_t* n_blocked_out,
                                  mpc_result_t* out, mpc_stream_t stream);
 
+/*
+ * Keep-out polygons: convex barriers beside the circles, in the one-shot
+ * expansion and arg-min.
+ *   - A keep-out polygon has 3 to MPC_MAX_POLYGON_VERTICES vertices in world
+ *     coordinates, is strictly convex and simple, and may be given in either
+ *     orientation; at most MPC_MAX_POLYGONS per call.  A non-convex barrier is
+ *     passed as several convex pieces.
+ *   - A candidate is BLOCKED if for any step k = 1..n_steps and any polygon its
+ *     state after step k lies strictly inside that polygon — on the inner side
+ *     of every edge's line — or inside any circle of the same call (above).
+ *     The start pose is not tested and the path between steps is not: the
+ *     caller inflates the polygon for the robot's size and for the distance
+ *     covered in one step.  A NaN state is inside nothing.
+ *   - The edge test is the half-plane form a x + b y + c > 0, evaluated as
+ *     fma(a, x, fma(b, y, c)): (a, b) is the edge line's unit inner normal and
+ *     c = -(a Px + b Py) for the edge's first endpoint P, all three formed once
+ *     per call on the host, so the value is the state's signed distance from
+ *     the line.  Its error — the roundings of a, b and c and of the two fused
+ *     operations — is below 4 * 2^-52 * (|x| + |y| + |Px| + |Py|): a state
+ *     further than that from every edge line (1e-14 for coordinates up to 10)
+ *     is judged as in exact arithmetic.  In MPC_HEADING_CUMULATIVE mode the
+ *     test runs on the step recurrence's sums: each line is moved into the
+ *     start-pose frame once per call (a line stays a line), and with L a power
+ *     of two and the sums scaled by 1/L the constant term is scaled by 1/L —
+ *     the same inequality divided by L > 0; the bound then also carries the
+ *     sums' own distance from the state that cum_pose forms of them (a few
+ *     ulps of the coordinates).
+ *   - A blocked candidate never wins; if all are blocked the result is the
+ *     "no finite cost" result (index -1, found 0).  Ties and the incumbent
+ *     test are those of mpc_rollout_argmin.
+ *   - n_blocked_out counts the candidates blocked by a circle or a polygon;
+ *     one blocked by both counts once.
+ *   - n_polygons == 0 calls mpc_rollout_partials_obstacles (and with
+ *     n_obstacles == 0 as well that launches the kernels of
+ *     mpc_rollout_partials): the same result byte for byte.
+ *   polygons       host array of n_polygons polygons, read during the call only
+ *                  (the edge tables travel as kernel arguments: a captured
+ *                  graph keeps them)
+ * The other arguments are those of mpc_rollout_partials_obstacles /
+ * mpc_rollout_argmin_obstacles (mpc_rollout_argmin_keepout =
+ * mpc_rollout_partials_keepout + mpc_rollout_finalize).  MPC_ERR_ARG, before
+ * any HIP call, after the checks of the circle entry in their order:
+ * n_polygons outside [0, MPC_MAX_POLYGONS], polygons NULL with n_polygons > 0,
+ * n_vertices outside [3, MPC_MAX_POLYGON_VERTICES], a non-finite vertex, or a
+ * polygon that is not strictly convex and simple — one condition: after
+ * normalising the orientation by the sign of the shoelace area, every vertex
+ * other than an edge's two endpoints lies strictly on the inner side of that
+ * edge's line (so a zero or non-finite area, a repeated vertex, a collinear
+ * triple, a reflex vertex, a bow-tie and a pentagram are all refused).  With
+ * valid tables every other rejection is the circle entry's.
+ * Polygons are taken by these two entries only: the device-resident episode
+ * steps (chained, generated, persistent, exchange and P2P steps included), the
+ * batched one-shot entry, the batched robots, the fleet and the full tree take
+ * none; neither are non-convex polygons as one object, swept (between-step)
+ * collision, soft penalties, or more than MPC_MAX_POLYGONS polygons of
+ * MPC_MAX_POLYGON_VERTICES vertices provided.
+ */
+#define MPC_MAX_POLYGONS 4
+#define MPC_MAX_POLYGON_VERTICES 8
+typedef struct mpc_polygon {
+  int32_t n_vertices, reserved_;
+  double x[MPC_MAX_POLYGON_VERTICES], y[MPC_MAX_POLYGON_VERTICES];
+} mpc_polygon_t; /* 136 B */
+
+int mpc_rollout_partials_keepout(const mpc_problem_t* p, const mpc_obstacle_t* obstacles,
+                                 int32_t n_obstacles, const mpc_polygon_t* polygons,
+                                 int32_t n_polygons, const double* v_sc, const double* beta_sc,
+                                 int64_t n_cand, int32_t n_steps, int32_t integrator,
+                                 double* states_out, void* ws, size_t ws_bytes,
+                                 int64_t* n_blocked_out, mpc_stream_t stream);
+int mpc_rollout_argmin_keepout(const mpc_problem_t* p, const mpc_obstacle_t* obstacles,
+                               int32_t n_obstacles, const mpc_polygon_t* polygons,
+                               int32_t n_polygons, const double* v_sc, const double* beta_sc,
+                               int64_t n_cand, int32_t n_steps, int64_t index_base,
+                               double incumbent, int32_t integrator, double* states_out, void* ws,
+                               size_t ws_bytes, int64_t* n_blocked_out, mpc_result_t* out,
+                               mpc_stream_t stream);
+
 /* Batched robots: R problems, robot r owns columns
  * [r*cand_per_problem, (r+1)*cand_per_problem) of the [n_steps][R*cand] SoA.
  * problems / incumbents (nullable => +inf) / out are device arrays of R.
