@@ -159,6 +159,36 @@ def replica_rollout(problem, v_sc, b_sc, integ="rect", device_estimates=False,
     return states, costs
 
 
+def replica_cum_sums(problem, v_sc, b_sc, device_estimates=False):
+    """The rect+cum recurrence's sums after every step, as the lane hook's loop()
+    sees them -> (sums [N,2,C], bad [C] bool), one-shot (host) constants;
+    device_estimates as replica_rollout."""
+    v_sc = np.ascontiguousarray(v_sc, dtype=np.float64)
+    b_sc = np.ascontiguousarray(b_sc, dtype=np.float64)
+    ns, n = v_sc.shape
+    sums, bad = np.empty((ns, 2, n)), np.full(n, 7, dtype=np.uint8)
+    L = replica_lib()
+    L.replica_cum_sums.argtypes = [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P]
+    L.replica_cum_sums.restype = None
+    if device_estimates:            # every denominator of b_sc, a NaN's too: replica_rollout's table
+        q = np.empty_like(np.unique(b_sc))
+        L.replica_tan_q(np.unique(b_sc).ctypes.data_as(_P), len(q), q.ctypes.data_as(_P))
+        q = np.unique(q)
+        r = device_rcp(q)
+        L.replica_set_rcp_table(q.ctypes.data_as(_P), r.ctypes.data_as(_P), len(q))
+    try:
+        L.replica_cum_sums(ctypes.byref(problem), v_sc.ctypes.data_as(_P),
+                           b_sc.ctypes.data_as(_P), n, ns, sums.ctypes.data_as(_P),
+                           bad.ctypes.data_as(_P))
+        if device_estimates:
+            assert L.replica_rcp_misses() == 0, "a denominator without its device estimate"
+    finally:
+        if device_estimates:
+            L.replica_set_rcp_table(None, None, 0)
+    assert set(np.unique(bad)) <= {0, 1}
+    return sums, bad.astype(bool)
+
+
 def _install_device_estimates(L, beta):
     """The device's reciprocal estimates of every tan_small denominator of beta."""
     beta = np.unique(np.ascontiguousarray(beta, dtype=np.float64))

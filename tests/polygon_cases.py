@@ -6,16 +6,25 @@ in numpy from the oracle's [N, 3, C] states with the header's real-number rule
 inside a circle of the same call), and the expected winner is the lowest (cost,
 index) among the unblocked candidates.  A case is computed once and shared
 (read-only arrays).  rejected_polygons(): the polygon arguments the keep-out
-entries refuse (tests/test_polygons_abi.py)."""
+entries refuse (tests/test_polygons_abi.py).
+
+Off the origin: PLACEMENTS, the start poses and wheelbases of the moved scenes
+(placed_problem, placed_case), and the exact rule they are judged by
+(exact_edge_distances, exact_inside: rational side of every edge line, mpmath
+distance), with the header's bound of the edge test (header_bound); host(),
+host_tables, host_inside, sums_of: the host build of the tables and of the lane
+hook's predicate (tests/polygon_harness.cpp)."""
+import ctypes
 import functools
 import math
+from fractions import Fraction as F
 from types import SimpleNamespace
 
 import numpy as np
 
 import obstacle_cases as oc
-from diplomjourney_amd.abi import (MPC_MAX_POLYGON_VERTICES, MPC_MAX_POLYGONS, MpcPolygon,
-                                   make_problem)
+from diplomjourney_amd.abi import (MPC_MAX_POLYGON_VERTICES, MPC_MAX_POLYGONS, MPC_OK, MpcPolygon,
+                                   MpcProblem, make_polygons, make_problem)
 
 MARGIN = oc.MARGIN
 
@@ -44,6 +53,174 @@ def edge_distances(x, y, poly):
 def inside(x, y, poly):
     """Strictly inside: on the inner side of every edge's line."""
     return (edge_distances(x, y, poly) > 0).all(axis=0)
+
+
+# ---------------------------------------------------------------------------
+# the exact rule
+# ---------------------------------------------------------------------------
+def _exact_edge(px, py, qx, qy, x, y, sgn):
+    """Signed distance of the double (x, y) from the line through the double
+    vertices P, Q (positive on the inner side): the cross product in rational
+    arithmetic, so its sign is exact, divided by the edge's length in mpmath
+    (50 digits) and rounded once to a double."""
+    import mpmath
+    dx, dy = F(qx) - F(px), F(qy) - F(py)
+    cross = sgn * (dx * (F(y) - F(py)) - dy * (F(x) - F(px)))
+    if cross == 0:
+        return 0.0
+    with mpmath.workprec(170):
+        d = mpmath.mpf(cross.numerator) / mpmath.mpf(cross.denominator) / mpmath.sqrt(
+            mpmath.mpf((dx * dx + dy * dy).numerator) / mpmath.mpf((dx * dx + dy * dy).denominator))
+        out = float(d)
+    assert out != 0.0 and (out > 0) == (cross > 0)
+    return out
+
+
+def exact_edge_distances(x, y, poly):
+    """edge_distances in exact arithmetic: [n_edges, ...] doubles whose sign is
+    the true sign of every state's side of every edge line of the double
+    vertices, and whose value is the true distance rounded once (0.0 only on the
+    line itself).  The float64 formula serves where it cannot be wrong: its
+    rounding error is below 8 * 2^-53 times |P - state|_1 (two differences, two
+    products, their difference, the length and the quotient), and a value above
+    2^-30 times that keeps it; every other value is replaced by _exact_edge's.
+    A NaN state gives NaN."""
+    P = [(float(px), float(py)) for px, py in poly]
+    Q = P[1:] + P[:1]
+    area2 = sum(F(px) * F(qy) - F(qx) * F(py) for (px, py), (qx, qy) in zip(P, Q))
+    assert area2 != 0
+    sgn = 1 if area2 > 0 else -1
+    shape = np.shape(x)
+    x, y = np.ravel(np.asarray(x, dtype=np.float64)), np.ravel(np.asarray(y, dtype=np.float64))
+    out = []
+    for (px, py), (qx, qy) in zip(P, Q):
+        dx, dy = qx - px, qy - py
+        with np.errstate(invalid="ignore", over="ignore"):
+            d = sgn * (dx * (y - py) - dy * (x - px)) / math.hypot(dx, dy)
+            near = np.abs(d) <= 2.0 ** -30 * (np.abs(x - px) + np.abs(y - py))
+        for i in np.flatnonzero(near):
+            d[i] = _exact_edge(px, py, qx, qy, float(x[i]), float(y[i]), sgn)
+        out.append(d.reshape(shape))
+    return np.stack(out)
+
+
+def header_bound(x, y, poly):
+    """include/mpc_rollout.h's bound of the edge test's error, per edge and
+    state [n_edges, ...]: 4 * 2^-52 * (|x| + |y| + |Px| + |Py|), P the edge's
+    first endpoint in the counter-clockwise order of the table."""
+    P = np.asarray(poly, dtype=np.float64)
+    Q = np.roll(P, -1, axis=0)
+    if float(np.sum(P[:, 0] * Q[:, 1] - Q[:, 0] * P[:, 1])) < 0:
+        # a clockwise list is reversed by the table's builder: edge i of the list
+        # (P_i -> P_i+1) is the table's edge from P_i+1 to P_i
+        P = Q
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.stack([4 * 2.0 ** -52 * (np.abs(x) + np.abs(y) + abs(px) + abs(py))
+                         for px, py in P])
+
+
+def exact_inside(x, y, polygons, extra=0.0):
+    """(inside [...], judged [...]): the exact rule over a call's polygons, and
+    where it binds the kernels — every edge line of every polygon further from
+    the state than the header's bound plus `extra`.  A NaN state is inside
+    nothing and judged."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    ins = np.zeros(x.shape, dtype=bool)
+    judged = np.ones(x.shape, dtype=bool)
+    for g in polygons:
+        d = exact_edge_distances(x, y, g)
+        with np.errstate(invalid="ignore"):
+            ins |= (d > 0).all(axis=0)
+            judged &= ~(np.abs(d) <= header_bound(x, y, g) + extra).any(axis=0)
+    return ins, judged
+
+
+# ---------------------------------------------------------------------------
+# placements: the start poses and wheelbases of the moved scenes
+# ---------------------------------------------------------------------------
+# (x, y, phi, L).  The ranking module's START; order 10 in two other quadrants
+# with the divided wheelbase forms (unscaled sums); phi = pi/2 exactly (c0 is
+# 6e-17); a heading beyond pi; a second power-of-two wheelbase (the sums scaled
+# by 1/L = 4); order 1000, where c = a Kx + b Ky + w.c cancels worst.
+PLACEMENTS = {
+    "start": (0.2, -0.1, 0.7, 0.5),
+    "ten-II": (-12.3, 9.7, 2.5, 0.45),
+    "ten-III": (-14.1, -11.6, -2.0, 0.3),
+    "pi/2": (3.3, -2.6, math.pi / 2, 0.5),
+    "phi=4": (-1.7, 2.9, 4.0, 0.45),
+    "L=1/4": (6.4, 7.7, -0.9, 0.25),
+    "thousand": (900.0, -700.0, 1.0, 0.5),
+}
+# the target of a placed problem, in the pose's own frame: ranking.TARGET seen from ranking.START
+_AHEAD = math.hypot(2.5, 3.1)
+_BEARING = math.atan2(3.1, 2.5) - 0.7
+
+
+def placed_problem(name, t_a=0.05, t_b=0.10):
+    """The problem of a placement: the target _AHEAD metres ahead, _BEARING left
+    of the heading, the line's origin at the pose — ranking.problem's scene seen
+    from the pose ("start" is ranking.problem(0.5) itself)."""
+    x, y, phi, L = PLACEMENTS[name]
+    if name == "start":
+        xt, yt = 2.7, 3.0
+    else:
+        xt, yt = x + _AHEAD * math.cos(phi + _BEARING), y + _AHEAD * math.sin(phi + _BEARING)
+    return make_problem(x, y, phi, xt, yt, x, y, L, t_a, t_b)
+
+
+def ahead(name, dist, off):
+    """The point `dist` ahead of a placement's pose, `off` rad left of its heading."""
+    x, y, phi, _ = PLACEMENTS[name]
+    return (x + dist * math.cos(phi + off), y + dist * math.sin(phi + off))
+
+
+def placed_polygons(name, winner, on, reach):
+    """(specs, polygons) of a placement, in the style of case(): (a) a CCW octagon
+    on the state (x, y) `winner`, R = 0.12 reach; (b) a CW triangle at 0.45 reach,
+    0.1 rad right of the heading, R = 0.08 reach; (c) a CW pentagon on the state
+    `on`, R = 0.05 reach; (d) a square 7 m ahead, R = 0.5, never reached.  Every
+    rotation is relative to the heading; the two states come from whatever
+    reference the caller compares with, computed at this pose."""
+    phi = PLACEMENTS[name][2]
+    specs = [((float(winner[0]), float(winner[1])), 0.12 * reach, 8, phi + 0.3, False),
+             (ahead(name, 0.45 * reach, -0.1), 0.08 * reach, 3, phi + 1.0, True),
+             ((float(on[0]), float(on[1])), 0.05 * reach, 5, phi + 0.1, True),
+             (ahead(name, 7.0, 0.8), 0.5, 4, phi, False)]
+    return specs, [ngon(*s) for s in specs]
+
+
+@functools.lru_cache(maxsize=None)
+def placed_case(name, n_cand=2178, n_steps=3):
+    """The oracle's rect states of obstacle_cases' controls from a placement's
+    pose, with that placement's polygons: the octagon on the unconstrained
+    winner's final state, the pentagon on candidate n_cand // 2 + 1's state
+    after step 2 (of 3)."""
+    from oracle import oracle as O
+    v, b = oc.controls(n_cand, n_steps, oc.SEED)
+    p = placed_problem(name)
+    res0, costs, states = O.rollout_argmin(p, v, b, integ="rect", want_costs=True,
+                                           want_states=True)
+    on = n_cand // 2 + 1
+    specs, polygons = placed_polygons(name, states[-1, :2, res0.index],
+                                      states[min(1, n_steps - 1), :2, on], 0.05 * n_steps)
+    oc._freeze(v, b, costs, states)
+    return SimpleNamespace(name=name, n_cand=n_cand, n_steps=n_steps, problem=p, v=v, b=b,
+                           costs=costs, states=states, specs=specs, polygons=polygons, res0=res0)
+
+
+def square_through(state, n_angle, h, delta=0.0):
+    """The CCW square of half-side h one of whose edge lines passes at signed
+    distance delta (positive: the state inside) from `state`, with inner normal
+    n = (cos, sin)(n_angle): centre state + (h - delta) n, sides along n and
+    across it.  The state lies h from the two side edges' lines and 2h - delta
+    from the far one's; after the vertices are rounded to doubles the near
+    distance is whatever the exact rule says."""
+    nx, ny = math.cos(n_angle), math.sin(n_angle)
+    cx, cy = state[0] + (h - delta) * nx, state[1] + (h - delta) * ny
+    tx, ty = -ny, nx
+    return [(cx + h * (a * nx + b * tx), cy + h * (a * ny + b * ty))
+            for a, b in ((-1, -1), (1, -1), (1, 1), (-1, 1))]
 
 
 def polygon_mask(states, polygons):
@@ -150,6 +327,75 @@ def check_preconditions(c):
         others = [q[:, c.irr] for k, q in enumerate(in_poly) if k != 2]
         assert not any(q.any() for q in others)
         assert in_poly[2][:-1, c.irr].any() and not in_poly[2][-1, c.irr] and c.mask[c.irr]
+
+
+# ---------------------------------------------------------------------------
+# the host build of the tables and the predicate (tests/polygon_harness.cpp)
+# ---------------------------------------------------------------------------
+_P = ctypes.c_void_p
+SLOTS = MPC_MAX_POLYGONS * MPC_MAX_POLYGON_VERTICES
+
+
+@functools.lru_cache(maxsize=None)
+def host():
+    import harness
+    L = harness.host_lib("polygon_harness")
+    L.poly_check.argtypes = [_P, ctypes.c_int]
+    L.poly_consts.argtypes = [ctypes.POINTER(MpcProblem), _P]
+    L.poly_tables.argtypes = [ctypes.POINTER(MpcProblem), _P, ctypes.c_int, _P, _P]
+    L.poly_inside.argtypes = [_P, ctypes.c_int, _P, ctypes.c_int64, _P]
+    L.poly_cum_pose.argtypes = [ctypes.POINTER(MpcProblem), _P, ctypes.c_int64, _P]
+    return L
+
+
+def host_tables(p, polygons):
+    """(world, loop): every slot (a, b, c) of the two tables of a call, [32, 3] each."""
+    arr, n = make_polygons(polygons)
+    assert host().poly_check(arr, n) == MPC_OK
+    world, loop = np.full((SLOTS, 3), np.nan), np.full((SLOTS, 3), np.nan)
+    host().poly_tables(ctypes.byref(p), arr, n, world.ctypes.data_as(_P), loop.ctypes.data_as(_P))
+    return world, loop
+
+
+def host_inside(table, n_poly, xy):
+    """inside_polygons (csrc/mpc_keepout.h) of the points xy [n, 2]: the lane hook's rule."""
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    out = np.full(len(xy), 7, dtype=np.uint8)
+    host().poly_inside(table.ctypes.data_as(_P), n_poly, xy.ctypes.data_as(_P), len(xy),
+                       out.ctypes.data_as(_P))
+    assert set(np.unique(out)) <= {0, 1}
+    return out.astype(bool)
+
+
+def host_consts(p):
+    """(Kx, Ky, s0, c0, inv_L, L_pow2, L) of the one-shot entries' constants."""
+    K = np.zeros(7)
+    host().poly_consts(ctypes.byref(p), K.ctypes.data_as(_P))
+    return K
+
+
+def host_cum_pose(p, ab):
+    """cum_pose of the sums ab [n, 2] (scaled sums when L is a power of two) -> [n, 2]."""
+    ab = np.ascontiguousarray(ab, dtype=np.float64)
+    back = np.empty_like(ab)
+    host().poly_cum_pose(ctypes.byref(p), ab.ctypes.data_as(_P), len(ab), back.ctypes.data_as(_P))
+    return back
+
+
+def sums_of(p, xy):
+    """(ab, err): the sums (A, B) — scaled by 1/L when L is a power of two — of
+    which cum_pose makes the points xy [n, 2], formed in float64, and the largest
+    distance |cum_pose(ab) - xy| over the points: the sums' own distance from
+    the state, which the header's bound of the rect+cum test carries."""
+    kx, ky, s0, c0, inv_l, pow2, _ = host_consts(p)
+    dx, dy = xy[:, 0] - kx, xy[:, 1] - ky
+    ab = np.stack([c0 * dx + s0 * dy, c0 * dy - s0 * dx], axis=1)
+    if pow2:
+        ab = ab * inv_l
+    back = host_cum_pose(p, ab)
+    with np.errstate(invalid="ignore"):
+        err = np.hypot(back[:, 0] - xy[:, 0], back[:, 1] - xy[:, 1])
+    return np.ascontiguousarray(ab), float(np.nanmax(err)) if len(err) else 0.0
 
 
 # ---------------------------------------------------------------------------

@@ -12,7 +12,9 @@ first mismatch names the candidate, hence its tile, wave, lane and pair slot.
 peel() is the driver (public ABI and production binaries only, no host
 synchronisation per peel), check_ranking() the comparison, controls() the fixed
 seeded input of a horizon, check_preconditions() what is asserted of the
-replica's numbers before a kernel is looked at.
+replica's numbers before a kernel is looked at.  polygon_case() is one case of
+the keep-out polygon kernels (tests/test_ranking_polygons_gpu.py): scene,
+expected mask and its conditions.
 """
 import functools
 import math
@@ -265,6 +267,217 @@ def blocked(states, circ):
             m |= (d2 < r * r).any(axis=0)
             margin = min(margin, float(np.nanmin(np.abs(np.sqrt(d2) - r))))
     return m, margin
+
+
+# ----------------------------------------------------------------------------
+# keep-out polygons (tests/test_ranking_polygons_gpu.py, test_ranking_cpu.py)
+# ----------------------------------------------------------------------------
+IRR_BLOCKED = 201      # the beta_irregular candidate the pentagon sits on (beta = -1.15 at step 0)
+
+
+def placed_circles(name, states, winner, n_steps):
+    """circles() seen from a placement of polygon_cases.PLACEMENTS ("start":
+    circles() itself): (c) 7 m ahead, 0.8 rad left, where the never-reached
+    square is."""
+    import polygon_cases as pc
+    if name == "start":
+        return circles(states, winner, n_steps)
+    reach = 0.05 * n_steps
+    return [(float(states[-1, 0, winner]), float(states[-1, 1, winner]), 0.10 * reach),
+            (*pc.ahead(name, 0.45 * reach, -0.1), 0.05 * reach),
+            (*pc.ahead(name, 7.0, 0.8), 0.5)]
+
+
+def polygon_scene(name, states, costs, inp, n_steps, n_poly=4, through=None):
+    """The polygons ranked at a placement, placed from the replica's states at
+    that pose and sized by the cloud of the regular candidates (speeds within
+    5 % of 0.5 m/s: after N steps a patch 0.0025 N m long and a few mm wide,
+    0.025 N m ahead), reach = 0.05 N:
+    (a) a CCW octagon on the unconstrained winner's final state, R = 0.12 reach
+        (the winner is the fast candidate 1025, metres ahead of the cloud);
+    (b) a CW triangle in the final cloud, 0.3 of the way along its bounding box
+        from the low corner, R = 0.25 of the box's diagonal;
+    (c) a CW pentagon on candidate IRR_BLOCKED's state after step 2 (step 1 for
+        N = 1) that reaches 0.9 of the way to the middle of the regular
+        candidates' states of that step;
+    (d) a CCW square 7 m ahead, R = 0.5, never reached — or, through = (candidate,
+        step): a square of half-side 0.3 reach with an edge line through that
+        state itself, its inner normal 0.4 rad left of the heading, so that the
+        rounded vertices leave the state within an ulp or two of the line, on
+        whichever side.
+    Rotations are relative to the heading.  -> (specs, polygons), the first
+    n_poly; a spec is (centre, R, n, rot, cw) or None for the square through a
+    state."""
+    import polygon_cases as pc
+    phi = pc.PLACEMENTS[name][2]
+    reach = 0.05 * n_steps
+    w = int(expected_order(costs)[0])
+    regular = np.isfinite(costs)
+    regular[list(inp.beta_irregular) + list(inp.dphi_irregular)] = False
+    fx, fy = states[-1, 0, regular], states[-1, 1, regular]
+    lo, hi = np.array([fx.min(), fy.min()]), np.array([fx.max(), fy.max()])
+    k = min(1, n_steps - 1)
+    on = states[k, :2, IRR_BLOCKED]
+    mid = np.array([np.median(states[k, 0, regular]), np.median(states[k, 1, regular])])
+    specs = [((float(states[-1, 0, w]), float(states[-1, 1, w])), 0.12 * reach, 8, phi + 0.3,
+              False),
+             (tuple(float(q) for q in lo + 0.3 * (hi - lo)), 0.25 * float(np.hypot(*(hi - lo))), 3,
+              phi + 1.0, True),
+             ((float(on[0]), float(on[1])), 0.9 * float(np.hypot(*(mid - on))), 5, phi + 0.1, True),
+             (pc.ahead(name, 7.0, 0.8), 0.5, 4, phi, False)]
+    polys = [pc.ngon(*q) for q in specs]
+    if through is not None:
+        c, kk = through
+        polys[3] = pc.square_through(states[kk, :2, c], phi + 0.4, 0.3 * reach)
+        specs[3] = None
+    return specs[:n_poly], polys[:n_poly]
+
+
+def host_polygon_mask(p, polygons, mode, states, sums=None, bad=None):
+    """[N, C]: the lane hook's verdict on every state, by the host build of its
+    own functions (csrc/mpc_keepout.h through tests/polygon_harness.cpp): the
+    world table on the replica's states — and for rect+cum the frame table on
+    the recurrence's sums (harness.replica_cum_sums), except a `bad` candidate,
+    whose recomputed states meet the world table.  No margin anywhere: two fma
+    and a compare are the same on both sides."""
+    import polygon_cases as pc
+    N, _, C = states.shape
+    world, loop = pc.host_tables(p, polygons)
+    flat = np.stack([states[:, 0, :].ravel(), states[:, 1, :].ravel()], axis=1)
+    in_world = pc.host_inside(world, len(polygons), flat).reshape(N, C)
+    if mode != "rect+cum":
+        return in_world     # (the launch's loop table is the world table)
+    flat = np.stack([sums[:, 0, :].ravel(), sums[:, 1, :].ravel()], axis=1)
+    in_loop = pc.host_inside(loop, len(polygons), flat).reshape(N, C)
+    return np.where(bad[None, :], in_world, in_loop)
+
+
+def sums_distance(p, states, sums, bad):
+    """rect+cum: cum_pose of the sums must be the replica's state bit for bit
+    (the export is the replica's own recurrence); -> the largest distance of a
+    state from the real-number image x0 + c0 A - s0 B, y0 + s0 A + c0 B of its
+    sums, which is what the frame table judges — the "sums' own distance from
+    the state" of the header's rect+cum bound — formed in long double."""
+    import polygon_cases as pc
+    N, _, C = states.shape
+    ok = ~bad & np.isfinite(states[:, 0, :]).all(axis=0)
+    ab = np.stack([sums[:, 0, :][:, ok].ravel(), sums[:, 1, :][:, ok].ravel()], axis=1)
+    xy = np.stack([states[:, 0, :][:, ok].ravel(), states[:, 1, :][:, ok].ravel()], axis=1)
+    back = pc.host_cum_pose(p, ab)
+    assert back.tobytes() == np.ascontiguousarray(xy).tobytes(), "the sums are not the replica's"
+    kx, ky, s0, c0, _, pow2, L = (np.longdouble(q) for q in pc.host_consts(p))
+    A, B = np.longdouble(ab[:, 0]), np.longdouble(ab[:, 1])
+    if pow2:
+        A, B = A * L, B * L
+    ex, ey = kx + (c0 * A - s0 * B) - np.longdouble(xy[:, 0]), \
+        ky + (s0 * A + c0 * B) - np.longdouble(xy[:, 1])
+    return float(np.hypot(ex, ey).max())
+
+
+def polygon_case(name, mode, n_steps, n=N_CAND, n_poly=4, mixed=False, plant=False, device=False):
+    """One ranked keep-out case: the fixed input of the horizon from a
+    placement's pose, the replica's states, costs and (rect+cum) sums — with the
+    device's reciprocal estimates when device, so bit for bit the kernel's — the
+    scene's polygons placed from them, and the expected mask, checked by
+    check_polygon_scene.  plant: the far square gives way to one with an edge
+    line through the final state of the best regular candidate the other three
+    polygons leave free.  mixed: plus placed_circles."""
+    import polygon_cases as pc
+    from harness import replica_cum_sums, replica_rollout
+    inp = controls(n_steps, n)
+    p = pc.placed_problem(name)
+    st, costs = replica_rollout(p, inp.v, inp.b, mode, device_estimates=device)
+    n_fin = check_preconditions(inp, costs)
+    assert n_fin == n - 3
+    sums = bad = None
+    extra = 0.0
+    if mode == "rect+cum":
+        sums, bad = replica_cum_sums(p, inp.v, inp.b, device_estimates=device)
+        assert bad[list(inp.beta_irregular)].all() and bad.sum() < 20
+        extra = sums_distance(p, st, sums, bad)
+    through = None
+    if plant:
+        _, three = polygon_scene(name, st, costs, inp, n_steps, 3)
+        taken = host_polygon_mask(p, three, mode, st, sums, bad).any(axis=0)
+        taken[list(inp.beta_irregular) + list(inp.dphi_irregular)] = True   # a regular one: loop()
+        through = (int(expected_order(costs, excluded=taken)[0]), n_steps - 1)
+    specs, polygons = polygon_scene(name, st, costs, inp, n_steps, n_poly, through)
+    per_state = host_polygon_mask(p, polygons, mode, st, sums, bad)
+    circ = placed_circles(name, st, int(expected_order(costs)[0]), n_steps) if mixed else []
+    what = f"{name} {mode} N={n_steps}"
+    mask = check_polygon_scene(inp, st, costs, polygons, specs, per_state, extra, circ, through,
+                               strict=n_poly == 4, what=what)
+    return SimpleNamespace(name=name, mode=mode, inp=inp, problem=p, states=st, costs=costs,
+                           polygons=polygons, circles=circ, mask=mask, extra=extra,
+                           through=through, n_fin=n_fin,
+                           n_free=int((np.isfinite(costs) & ~mask).sum()), what=what)
+
+
+def check_polygon_scene(inp, states, costs, polygons, specs, per_state, extra=0.0, circ=(),
+                        through=None, strict=True, what=""):
+    """What a polygon case asserts of the reference before any launch.
+    per_state [N, C]: host_polygon_mask.  It must be the exact rule
+    (polygon_cases.exact_inside) on every state further from every edge line
+    than the header's bound plus `extra`; at most 1 % of the states are not so
+    judged (the `through` state is one of them and with N = 1 the only one) and a
+    blocked and a free candidate are.  Then the conditions on the mask: 10 to
+    90 % of the finite candidates blocked, the unconstrained winner among them,
+    one blocked at a step that is not its last while its last state is free (N >
+    1), a state inside a circumscribed circle and outside its polygon, every
+    polygon of the scene but the far square blocking somebody, IRR_BLOCKED
+    blocked and another beta_irregular candidate free.  circ: circles of the
+    same call — some candidate blocked by a circle alone, some by a polygon
+    alone, some by both.  -> the call's mask [C]."""
+    import polygon_cases as pc
+    N, _, C = states.shape
+    x, y = states[:, 0, :], states[:, 1, :]
+    want, judged = pc.exact_inside(x, y, polygons, extra=extra)
+    left_out = int((~judged).sum())
+    if through is not None:
+        assert not judged[through[1], through[0]], "the planted state is not within the bound"
+    assert left_out <= max(0.01 * judged.size, 1 if through is not None else 0), (what, left_out)
+    bad = (per_state != want) & judged
+    assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:5])
+    fully = judged.all(axis=0)
+    by_poly = per_state.any(axis=0)
+    assert (by_poly & fully).any() and (~by_poly & fully).any()
+    fin = np.isfinite(costs)
+    mask = by_poly.copy()
+    if len(circ):
+        by_circle, margin = blocked(states, circ)
+        assert margin > MARGIN, margin
+        assert (by_circle & ~by_poly).any() and (by_poly & ~by_circle).any() \
+            and (by_poly & by_circle).any(), what
+        mask |= by_circle
+    frac = (mask & fin).sum() / fin.sum()
+    print(f"{what}: {int((mask & fin).sum())} of {int(fin.sum())} finite candidates blocked, "
+          f"{left_out} of {judged.size} states within {extra:.3g} + the header's bound of an edge")
+    assert mask[int(expected_order(costs)[0])], "the unconstrained winner is not blocked"
+    each = [pc.exact_inside(x, y, [g])[0] for g in polygons]
+    if not strict:         # fewer polygons: every one of them blocks somebody, somebody is free
+        assert all(q.any() for q in each) and 0 < frac < 1, what
+        return mask
+    assert 0.10 <= frac <= 0.90, (what, frac)
+    if N > 1:
+        final_in = np.zeros(C, dtype=bool)
+        for q in each:
+            final_in |= q[-1]
+        assert (by_poly & ~final_in & fully).any(), what
+    for s, q in zip(specs, each):
+        if s is None:
+            continue
+        if s[1] != 0.5:
+            assert q.any(), (what, "a polygon blocks nobody")
+        else:
+            assert not q.any()
+    with np.errstate(invalid="ignore"):
+        assert any(((((x - s[0][0]) ** 2 + (y - s[0][1]) ** 2) < s[1] ** 2) & ~q).any()
+                   for s, q in zip(specs, each) if s is not None), what
+    irr = list(inp.beta_irregular)
+    if len(polygons) >= 3:
+        assert by_poly[IRR_BLOCKED], what
+    assert not by_poly[irr].all() and (by_poly[irr].any() or len(polygons) < 3), what
+    return mask
 
 
 # ----------------------------------------------------------------------------

@@ -103,6 +103,38 @@ extern "C" int replica_rollout_device_consts(const mpc_problem_t* p, const doubl
   return rollout_impl(p, v, b, n_cand, n_steps, integ, true, states, costs);
 }
 
+// The sums (A, B) of the rect+cum recurrence after every step — what a lane
+// hook's loop() is handed (tests/test_ranking_polygons_gpu.py: the keep-out
+// polygons' frame table is evaluated on them), scaled by 1/L when L is a power
+// of two — and the candidate's `bad` flag (its states then come from step_safe
+// and the hook tests those).  rollout_candidate_l's own loop, which keeps only
+// what cum_pose makes of the sums.  sums: [n_steps][2][n_cand].
+template <bool PL2>
+static void cum_sums(const mpc::Consts& K, const double* v, const double* b, int64_t n_cand,
+                     int32_t n_steps, double* sums, uint8_t* bad_out) {
+  for (int64_t col = 0; col < n_cand; ++col) {
+    double x, y, ph, s, c;
+    mpc::step_start<mpc::kRotCum>(K, x, y, ph, s, c);
+    bool bad = false;
+    for (int st = 0; st < n_steps; ++st) {
+      mpc::step_core<MPC_INTEG_RECT, mpc::kRotCum, PL2>(x, y, ph, s, c, v[st * n_cand + col],
+                                                        b[st * n_cand + col], K, bad);
+      sums[(st * 2 + 0) * n_cand + col] = x;
+      sums[(st * 2 + 1) * n_cand + col] = y;
+    }
+    bad_out[col] = bad ? 1 : 0;
+  }
+}
+
+extern "C" void replica_cum_sums(const mpc_problem_t* p, const double* v, const double* b,
+                                 int64_t n_cand, int32_t n_steps, double* sums, uint8_t* bad_out) {
+  const mpc::Consts K = mpc::host_consts(*p);
+  if (K.L_pow2)
+    cum_sums<true>(K, v, b, n_cand, n_steps, sums, bad_out);
+  else
+    cum_sums<false>(K, v, b, n_cand, n_steps, sums, bad_out);
+}
+
 // ---------------------------------------------------------------------------
 // The full tree (mpc_ftdevice.h): every leaf's cost in leaf order
 // j = (k0 * S1 + k1) * S1 + k2, by the functions the kernels run.

@@ -87,6 +87,38 @@ def test_big_positions_are_distinct_lane_pairs():
     assert sorted(c2) == sorted(costs) and sorted(v2[0]) == sorted(v[0])
 
 
+def _polygon_cases():
+    """Every case of tests/test_ranking_polygons_gpu.py, as polygon_case's arguments."""
+    import polygon_cases as pc
+    cases = [dict(name="start", mode=m, n_steps=N, plant=N == 3)
+             for m in R.MODES for N in (1, 3, 10)]
+    cases += [dict(name=name, mode=m, n_steps=3) for name in pc.PLACEMENTS if name != "start"
+              for m in ("rect", "rect+cum", "qk21+rot")]
+    cases += [dict(name=name, mode=m, n_steps=3, mixed=True) for name in ("start", "ten-II")
+              for m in ("rect", "rect+cum", "qk21")]
+    cases += [dict(name="start", mode=m, n_steps=N, n=n) for n in (1025, R.N_CAND)
+              for m in ("rect", "rect+cum") for N in (1, 3)]
+    cases += [dict(name="ten-III", mode="rect+cum", n_steps=3, n_poly=k) for k in (1, 2, 3)]
+    return cases
+
+
+def test_polygon_case_preconditions(oracle):
+    """What the keep-out polygon ranking cases assert of their reference before
+    a launch holds of the host replica without the device's estimates: the
+    scene's conditions, the host-built mask against the exact rule, and how few
+    states the header's bound leaves out (ranking.check_polygon_scene)."""
+    cases = _polygon_cases()
+    assert len(cases) == 15 + 18 + 6 + 8 + 3
+    total = 0
+    for kw in cases:
+        c = R.polygon_case(**kw)
+        assert 0 < c.n_free < c.n_fin
+        if c.through is not None:
+            assert c.through[0] not in c.inp.beta_irregular + c.inp.dphi_irregular
+        total += c.n_free
+    print(f"{len(cases)} cases, {total} candidates to rank")
+
+
 @pytest.mark.parametrize("n_steps", R.HORIZONS + (10,))
 def test_input_preconditions(oracle, n_steps):
     """Every problem the GPU cases rank, on the host replica."""
