@@ -3,7 +3,8 @@
 // math_model_tree.py:278-362).  Kernels: mpc_kernels.h (rollout + arg-min,
 // selection), mpc_finalize.h, mpc_sampler.h, and the device-resident episode's
 // (mpc_episode.h, mpc_generated.h, mpc_exchange.h, mpc_chain.h, mpc_run.h,
-// mpc_episode_obs.h: the steps with keep-out circles);
+// mpc_episode_obs.h: the steps with keep-out circles, mpc_episode_keepout.h:
+// with circles and polygons);
 // the host's problem constants: mpc_host_consts.h.
 //
 // HBM traffic of k_rollout_argmin: 16 B per candidate-step read once
@@ -27,6 +28,7 @@
 #include "mpc_device.h"
 #include "mpc_dispatch.h"
 #include "mpc_episode.h"
+#include "mpc_episode_keepout.h"
 #include "mpc_episode_obs.h"
 #include "mpc_episodes.h"
 #include "mpc_episodes_fleet_launch.h"
@@ -300,6 +302,59 @@ void launch_episode_obs(hipStream_t st, int32_t integrator, const Obstacles& W, 
   });
 }
 
+// The world tables of a keep-out episode call (kernel argument 0,
+// mpc_episode_keepout.h).
+EpisodeKeepoutArgs episode_keepout_args(const mpc_obstacle_t* obstacles, int n_obstacles,
+                                        const mpc_polygon_t* polygons, int n_polygons) {
+  return EpisodeKeepoutArgs{world_obstacles(obstacles, n_obstacles),
+                            world_polygons(polygons, n_polygons), n_polygons, {0, 0, 0}};
+}
+
+// launch_episode_obs with polygons as well (mpc_episode_keepout.h): the same
+// grid and path choice.  The circle count picks the instantiation: none
+// (polygons alone) or all 16 (unused circles are padded, never entered); the
+// scalar path has the 16 only.  These kernels are instantiated in this unit:
+// in mpc_episodes_obs.hip they moved the digests of 24 of that unit's kernels,
+// here of none (tools/kernel_digest.py).
+void launch_episode_keepout(hipStream_t st, int32_t integrator, const EpisodeKeepoutArgs& A,
+                            int n_obs, bool wide, int64_t grid, const Consts* Kdev,
+                            const double* v, const double* b, int64_t n_cand, int n_steps,
+                            Rec* part, unsigned long long* n_blocked) {
+  const dim3 g(static_cast<unsigned>(grid));
+  dispatch_mode(integrator, [&](auto I, auto R) {
+    constexpr int kAll = MPC_MAX_OBSTACLES;
+    if (!wide)
+      k_episode_argmin_keepout<I, R, kAll><<<g, kBlock, 0, st>>>(A, Kdev, v, b, n_cand, n_steps,
+                                                                 part, n_blocked);
+    else if (n_obs > 0)
+      k_episode_stream_keepout<I, R, kAll><<<g, kBlock, 0, st>>>(A, Kdev, v, b, n_cand, n_steps,
+                                                                 part, n_blocked);
+    else
+      k_episode_stream_keepout<I, R, 0><<<g, kBlock, 0, st>>>(A, Kdev, v, b, n_cand, n_steps, part,
+                                                              n_blocked);
+  });
+}
+
+// k_episode_chain_keepout<pl2, tiled, 0 | 16> on `tiles` + 1 blocks.
+void launch_episode_chain_keepout(hipStream_t st, bool pl2, bool tiled, int64_t tiles,
+                                  const EpisodeKeepoutArgs& A, int n_obs, EpisodeState* S,
+                                  uint32_t epoch, const double* v, const double* b, int64_t n_cand,
+                                  int n_steps, Rec* part, int has_prev, const Rec* part_prev,
+                                  int n_part_prev, const double* v_prev, const double* b_prev,
+                                  int64_t index_base, mpc_result_t* out_prev,
+                                  const mpc_episode_config_t& ecfg, mpc_episode_log_t* log, int cap,
+                                  unsigned long long* n_blocked) {
+  const dim3 g(static_cast<unsigned>(tiles + 1));
+  dispatch_bools(
+      [&](auto PL2, auto TILED, auto CIRCLES) {
+        k_episode_chain_keepout<PL2, TILED, CIRCLES ? MPC_MAX_OBSTACLES : 0>
+            <<<g, kBlock, 0, st>>>(A, S, epoch, v, b, n_cand, n_steps, part, has_prev, part_prev,
+                                   n_part_prev, v_prev, b_prev, index_base, out_prev, ecfg, log,
+                                   cap, n_blocked);
+      },
+      pl2, tiled, n_obs > 0);
+}
+
 // n_blocked_out of the episode obstacle entries: zeroed on the stream.
 int zero_blocked(int64_t* n_blocked_out, hipStream_t st) {
   if (n_blocked_out && hipMemsetAsync(n_blocked_out, 0, sizeof(*n_blocked_out), st) != hipSuccess)
@@ -419,21 +474,32 @@ EpisodeHook episode_hook(EpisodeState* S, bool advance, mpc_episode_log_t* log,
                      advance ? S->chain_pub : nullptr, advance ? kPubWords : 0};
 }
 
-// mpc_episode_partials (no circles, no count) and mpc_episode_partials_obstacles:
-// the circles are checked first, the count is zeroed once every check has
-// passed, and with no circles the plain kernels run (nothing can be blocked).
+// mpc_episode_partials (no circles, no count), mpc_episode_partials_obstacles
+// (no polygons) and mpc_episode_partials_keepout: the circles are checked
+// first, then the polygons, the count is zeroed once every check has passed;
+// with no polygons the circle kernels run, and with no circles either the
+// plain ones (nothing can be blocked).
 int episode_partials(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
-                     const double* v_sc, const double* beta_sc, int64_t n_cand, int32_t n_steps,
-                     int32_t integrator, void* ws, size_t ws_bytes, int64_t* n_blocked_out,
-                     mpc_stream_t stream) {
+                     const mpc_polygon_t* polygons, int32_t n_polygons, const double* v_sc,
+                     const double* beta_sc, int64_t n_cand, int32_t n_steps, int32_t integrator,
+                     void* ws, size_t ws_bytes, int64_t* n_blocked_out, mpc_stream_t stream) {
   if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
+  if (check_polygons(polygons, n_polygons) != MPC_OK) return MPC_ERR_ARG;
   if (check_episode_arrays(state, v_sc, beta_sc, n_cand, n_steps) != MPC_OK) return MPC_ERR_ARG;
   if (mode_ok(integrator) != MPC_OK) return MPC_ERR_UNSUPPORTED;
   if (!workspace_ok(ws, ws_bytes, n_cand, n_steps)) return MPC_ERR_WORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (zero_blocked(n_blocked_out, st) != MPC_OK) return MPC_ERR_HIP;
   EpisodeState* S = static_cast<EpisodeState*>(state);
-  if (n_obstacles == 0)
+  if (n_polygons > 0) {
+    const bool wide = wide_ok(v_sc, beta_sc, n_cand);
+    launch_episode_keepout(st, integrator,
+                           episode_keepout_args(obstacles, n_obstacles, polygons, n_polygons),
+                           n_obstacles, wide,
+                           wide ? rollout_grid<kCplWide>(n_cand) : rollout_grid<1>(n_cand),
+                           &S->h.K, v_sc, beta_sc, n_cand, n_steps, static_cast<Rec*>(ws),
+                           reinterpret_cast<unsigned long long*>(n_blocked_out));
+  } else if (n_obstacles == 0)
     launch_rollout<true>(st, integrator, Consts{}, &S->h.K, v_sc, beta_sc, n_cand, n_steps,
                          static_cast<Rec*>(ws));
   else
@@ -443,15 +509,18 @@ int episode_partials(void* state, const mpc_obstacle_t* obstacles, int32_t n_obs
   return last_hip_status();
 }
 
-// mpc_episode_chain_step and mpc_episode_chain_step_obstacles, in the same way.
+// mpc_episode_chain_step, mpc_episode_chain_step_obstacles and
+// mpc_episode_chain_step_keepout, in the same way.
 int episode_chain_step(const mpc_episode_config_t* cfg, void* state,
-                       const mpc_obstacle_t* obstacles, int32_t n_obstacles, int32_t mode,
+                       const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                       const mpc_polygon_t* polygons, int32_t n_polygons, int32_t mode,
                        uint32_t epoch, const double* v_sc, const double* beta_sc, int64_t n_cand,
                        int32_t n_steps, int64_t index_base, int32_t integrator, void* ws,
                        const void* ws_prev, size_t ws_bytes, const double* v_prev,
                        const double* beta_prev, mpc_result_t* out_prev, mpc_episode_log_t* log,
                        int32_t log_capacity, int64_t* n_blocked_out, mpc_stream_t stream) {
   if (check_obstacles(obstacles, n_obstacles) != MPC_OK) return MPC_ERR_ARG;
+  if (check_polygons(polygons, n_polygons) != MPC_OK) return MPC_ERR_ARG;
   int has_prev = 0;
   const int a = check_chain_step(cfg, state, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
                                  index_base, integrator, ws, ws_prev, ws_bytes, v_prev, beta_prev,
@@ -466,6 +535,15 @@ int episode_chain_step(const mpc_episode_config_t* cfg, void* state,
   const int n_part_prev = static_cast<int>(tiles);
   Rec* part = static_cast<Rec*>(ws);
   const Rec* part_prev = static_cast<const Rec*>(ws_prev);
+  if (n_polygons > 0) {
+    launch_episode_chain_keepout(
+        st, length_pow2(cfg->L), is_tiled(integrator), tiles,
+        episode_keepout_args(obstacles, n_obstacles, polygons, n_polygons), n_obstacles, S, epoch,
+        v_sc, beta_sc, n_cand, n_steps, part, has_prev, part_prev, n_part_prev, v_prev, beta_prev,
+        index_base, out_prev, *cfg, log, log_capacity,
+        reinterpret_cast<unsigned long long*>(n_blocked_out));
+    return last_hip_status();
+  }
   dispatch_bools(
       [&](auto PL2, auto TILED) {
         if (n_obstacles == 0)
@@ -992,8 +1070,8 @@ int mpc_episode_generate_step(const mpc_episode_config_t* cfg, void* state, int6
 int mpc_episode_partials(void* state, const double* v_sc, const double* beta_sc, int64_t n_cand,
                          int32_t n_steps, int32_t integrator, void* ws, size_t ws_bytes,
                          mpc_stream_t stream) {
-  return episode_partials(state, nullptr, 0, v_sc, beta_sc, n_cand, n_steps, integrator, ws,
-                          ws_bytes, nullptr, stream);
+  return episode_partials(state, nullptr, 0, nullptr, 0, v_sc, beta_sc, n_cand, n_steps, integrator,
+                          ws, ws_bytes, nullptr, stream);
 }
 
 int mpc_episode_finalize(void* state, const double* v_sc, const double* beta_sc, int64_t n_cand,
@@ -1032,8 +1110,8 @@ int mpc_episode_partials_obstacles(void* state, const mpc_obstacle_t* obstacles,
                                    const double* beta_sc, int64_t n_cand, int32_t n_steps,
                                    int32_t integrator, void* ws, size_t ws_bytes,
                                    int64_t* n_blocked_out, mpc_stream_t stream) {
-  return episode_partials(state, obstacles, n_obstacles, v_sc, beta_sc, n_cand, n_steps,
-                          integrator, ws, ws_bytes, n_blocked_out, stream);
+  return episode_partials(state, obstacles, n_obstacles, nullptr, 0, v_sc, beta_sc, n_cand,
+                          n_steps, integrator, ws, ws_bytes, n_blocked_out, stream);
 }
 
 int mpc_episode_step_obstacles(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
@@ -1046,6 +1124,30 @@ int mpc_episode_step_obstacles(void* state, const mpc_obstacle_t* obstacles, int
   const int a = mpc_episode_partials_obstacles(state, obstacles, n_obstacles, v_sc, beta_sc, n_cand,
                                                n_steps, integrator, ws, ws_bytes, n_blocked_out,
                                                stream);
+  if (a != MPC_OK) return a;
+  return mpc_episode_finalize(state, v_sc, beta_sc, n_cand, n_steps, index_base, integrator, ws,
+                              ws_bytes, out, advance, log, log_capacity, stream);
+}
+
+int mpc_episode_partials_keepout(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                                 const mpc_polygon_t* polygons, int32_t n_polygons,
+                                 const double* v_sc, const double* beta_sc, int64_t n_cand,
+                                 int32_t n_steps, int32_t integrator, void* ws, size_t ws_bytes,
+                                 int64_t* n_blocked_out, mpc_stream_t stream) {
+  return episode_partials(state, obstacles, n_obstacles, polygons, n_polygons, v_sc, beta_sc,
+                          n_cand, n_steps, integrator, ws, ws_bytes, n_blocked_out, stream);
+}
+
+int mpc_episode_step_keepout(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                             const mpc_polygon_t* polygons, int32_t n_polygons, const double* v_sc,
+                             const double* beta_sc, int64_t n_cand, int32_t n_steps,
+                             int64_t index_base, int32_t integrator, void* ws, size_t ws_bytes,
+                             mpc_result_t* out, const mpc_episode_config_t* advance,
+                             mpc_episode_log_t* log, int32_t log_capacity, int64_t* n_blocked_out,
+                             mpc_stream_t stream) {
+  const int a = mpc_episode_partials_keepout(state, obstacles, n_obstacles, polygons, n_polygons,
+                                             v_sc, beta_sc, n_cand, n_steps, integrator, ws,
+                                             ws_bytes, n_blocked_out, stream);
   if (a != MPC_OK) return a;
   return mpc_episode_finalize(state, v_sc, beta_sc, n_cand, n_steps, index_base, integrator, ws,
                               ws_bytes, out, advance, log, log_capacity, stream);
@@ -1083,7 +1185,7 @@ int mpc_episode_chain_step(const mpc_episode_config_t* cfg, void* state, int32_t
                            const double* v_prev, const double* beta_prev, mpc_result_t* out_prev,
                            const mpc_result_t* /*gathered*/, int32_t /*n_gathered*/,
                            mpc_episode_log_t* log, int32_t log_capacity, mpc_stream_t stream) {
-  return episode_chain_step(cfg, state, nullptr, 0, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
+  return episode_chain_step(cfg, state, nullptr, 0, nullptr, 0, mode, epoch, v_sc, beta_sc, n_cand, n_steps,
                             index_base, integrator, ws, ws_prev, ws_bytes, v_prev, beta_prev,
                             out_prev, log, log_capacity, nullptr, stream);
 }
@@ -1095,9 +1197,23 @@ int mpc_episode_chain_step_obstacles(
     const void* ws_prev, size_t ws_bytes, const double* v_prev, const double* beta_prev,
     mpc_result_t* out_prev, const mpc_result_t* /*gathered*/, int32_t /*n_gathered*/,
     mpc_episode_log_t* log, int32_t log_capacity, int64_t* n_blocked_out, mpc_stream_t stream) {
-  return episode_chain_step(cfg, state, obstacles, n_obstacles, mode, epoch, v_sc, beta_sc, n_cand,
-                            n_steps, index_base, integrator, ws, ws_prev, ws_bytes, v_prev,
-                            beta_prev, out_prev, log, log_capacity, n_blocked_out, stream);
+  return episode_chain_step(cfg, state, obstacles, n_obstacles, nullptr, 0, mode, epoch, v_sc,
+                            beta_sc, n_cand, n_steps, index_base, integrator, ws, ws_prev, ws_bytes,
+                            v_prev, beta_prev, out_prev, log, log_capacity, n_blocked_out, stream);
+}
+
+int mpc_episode_chain_step_keepout(
+    const mpc_episode_config_t* cfg, void* state, const mpc_obstacle_t* obstacles,
+    int32_t n_obstacles, const mpc_polygon_t* polygons, int32_t n_polygons, int32_t mode,
+    uint32_t epoch, const double* v_sc, const double* beta_sc, int64_t n_cand, int32_t n_steps,
+    int64_t index_base, int32_t integrator, void* ws, const void* ws_prev, size_t ws_bytes,
+    const double* v_prev, const double* beta_prev, mpc_result_t* out_prev,
+    const mpc_result_t* /*gathered*/, int32_t /*n_gathered*/, mpc_episode_log_t* log,
+    int32_t log_capacity, int64_t* n_blocked_out, mpc_stream_t stream) {
+  return episode_chain_step(cfg, state, obstacles, n_obstacles, polygons, n_polygons, mode, epoch,
+                            v_sc, beta_sc, n_cand, n_steps, index_base, integrator, ws, ws_prev,
+                            ws_bytes, v_prev, beta_prev, out_prev, log, log_capacity, n_blocked_out,
+                            stream);
 }
 
 #ifdef MPC_TIMELINE

@@ -8,7 +8,8 @@ import torch
 
 from . import native
 from .abi import (CANDIDATE_BYTES, INTEGRATORS, IPC_HANDLE_BYTES, LOG_BYTES, MPC_LAYOUT_TILED,
-                  MPC_MAX_OBSTACLES, MPC_TILE, RESULT_BYTES, MpcEpisodeLog, make_obstacles)
+                  MPC_MAX_OBSTACLES, MPC_MAX_POLYGONS, MPC_TILE, RESULT_BYTES, MpcEpisodeLog,
+                  make_obstacles, make_polygons, polygon_is_convex, polygon_vertices)
 from .distributed import gather_bytes, gather_into, gather_results, reduce_int, shard_range
 from .episode_config import ChainError, reference_episode_config
 from .streams import _check_overlap_stream
@@ -37,8 +38,8 @@ class _ChainForm:
 
 
 class _OneGpuChain(_ChainForm):
-    """mpc_episode_chain_step (with circles: _chain_step_obstacles) /
-    mpc_episode_finalize."""
+    """mpc_episode_chain_step (with circles: _chain_step_obstacles, with
+    polygons: _chain_step_keepout) / mpc_episode_finalize."""
     pends_controls = True
 
     def launch(self, ep, ctl, pend, events):
@@ -242,13 +243,24 @@ class DeviceEpisode:
     step with one (40.4 against 39.7 us); counting n_blocked adds ~5 us to
     either.  Not supported, ValueError: generate,
     split=False, the chained exchange / P2P / overlapped steps, run().  With no
-    circles every call is the one made without the feature."""
+    circles every call is the one made without the feature.
+
+    polygons / set_polygons(): convex keep-out polygons, each a sequence of 3
+    to 8 (x, y) vertices in either orientation, at most 4, beside the circles
+    and with the semantics of mpc_rollout_partials_keepout: strictly inside
+    blocks, one blocked by a circle and a polygon counts once in `n_blocked`.
+    The same step forms take them and the same ones refuse them; with no
+    polygons every call is the one made without them.  As with circles the
+    chained tile blocks wait for the step's pose first: at config C the
+    chained step is the faster form with one polygon (44.7 against 46.3 us per
+    step) and the slower one with four octagons (83.0 against 80.7 us)
+    (DESIGN.md §5)."""
 
     def __init__(self, engine, n_cand_total, n_steps, rank=0, world=1, seed=20261015,
                  integrator="rect", group=None, start=(0.0, 0.0, 0.0, 0.0, 0.0), target=(2, 3),
                  log_capacity=4096, split=True, exchange=None, chain=False, L=None,
                  generate=False, max_steps=0, incumbent0=0.0, enumerate=False, overlap=False,
-                 p2p=False, mailbox_uncached=True, obstacles=()):
+                 p2p=False, mailbox_uncached=True, obstacles=(), polygons=()):
         self.eng = engine
         self.lib = native.lib()           # entries that return their status (callers, tests)
         self._C = native.calls()          # entries that raise
@@ -293,7 +305,7 @@ class DeviceEpisode:
         self.chain = bool(chain)
         self._ws = [self.ws, torch.zeros_like(self.ws)] if self.chain else [self.ws]
         self.generate = bool(generate)
-        if len(obstacles) and not self._takes_obstacles():
+        if (len(obstacles) or len(polygons)) and not self._takes_obstacles():
             raise ValueError(self._OBSTACLE_FORMS)
         # exchange + chain: this rank's best candidate of the step (the
         # all_gather payload of mpc_episode_exchange_step)
@@ -331,11 +343,14 @@ class DeviceEpisode:
         self.steps_enqueued = 0
         self.n_blocked = torch.zeros(1, dtype=torch.int64, device=dev)
         self._obs, self._n_obs = None, 0
+        self._poly, self._n_poly = None, 0
         self.set_obstacles(obstacles)
+        self.set_polygons(polygons)
         self.reset(_fresh_mailbox=True)
 
-    _OBSTACLE_FORMS = ("keep-out circles: the two-launch step (split=True, generate=False) and "
-                       "the one-GPU chained step (chain=True, exchange=False) only")
+    _OBSTACLE_FORMS = ("keep-out circles and polygons: the two-launch step (split=True, "
+                       "generate=False) and the one-GPU chained step (chain=True, "
+                       "exchange=False) only")
 
     def set_obstacles(self, circles):
         """The keep-out circles of the steps enqueued from now on (a pending
@@ -350,6 +365,30 @@ class DeviceEpisode:
             self.flush()
         self._obs, self._n_obs = obs, n
 
+    @staticmethod
+    def checked_polygons(polygons):
+        """(MpcPolygon array or None, count) of the episode's polygons
+        (make_polygons), ValueError for more than MPC_MAX_POLYGONS and for one
+        the library's rule refuses (not strictly convex and simple)."""
+        rows = [polygon_vertices(g) for g in (polygons or ())]
+        if len(rows) > MPC_MAX_POLYGONS:
+            raise ValueError(f"at most {MPC_MAX_POLYGONS} polygons")
+        if not all(polygon_is_convex(g) for g in rows):
+            raise ValueError("a keep-out polygon is strictly convex and simple: split a "
+                             "non-convex or degenerate polygon into convex pieces")
+        return make_polygons(rows)
+
+    def set_polygons(self, polygons):
+        """The keep-out polygons of the steps enqueued from now on (a pending
+        chained step is completed first; its rollout already ran under the
+        previous polygons)."""
+        poly, n = self.checked_polygons(polygons)
+        if n and not self._takes_obstacles():
+            raise ValueError(self._OBSTACLE_FORMS)
+        if self._pending is not None:
+            self.flush()
+        self._poly, self._n_poly = poly, n
+
     def _takes_obstacles(self):
         return self.split and not self.generate and not (self.chain and self.exchange)
 
@@ -360,11 +399,24 @@ class DeviceEpisode:
             return None
         return self._obs, self._n_obs, self.n_blocked.data_ptr()
 
+    def _polygon_args(self):
+        """The second hook of _entry: None, or what the `_keepout` twins take
+        after the circles: (polygons, count)."""
+        if not self._n_poly:
+            return None
+        return self._poly, self._n_poly
+
     def _entry(self, name, head, *args):
         """The call site of the chained launch, the two-launch step and partials:
         entry `name`, or with circles its `_obstacles` twin, which takes them
-        after `head` (up to the state) and n_blocked_out before the stream."""
+        after `head` (up to the state) and n_blocked_out before the stream, or
+        with polygons its `_keepout` twin, which takes them after the circles."""
         extra = self._obstacle_args()
+        polys = self._polygon_args()
+        if polys is not None:
+            *circles, blocked = extra if extra is not None else (None, 0, self.n_blocked.data_ptr())
+            twin = getattr(self._C, name + "_keepout")
+            return twin(*head, *circles, *polys, *args[:-1], blocked, args[-1])
         if extra is None:
             return getattr(self._C, name)(*head, *args)
         *circles, blocked = extra
@@ -525,7 +577,7 @@ class DeviceEpisode:
         first."""
         if self.exchange:
             raise ValueError("the persistent run: one GPU (no exchange step)")
-        if self._n_obs:
+        if self._n_obs or self._n_poly:
             raise ValueError("run(): " + self._OBSTACLE_FORMS)
         if self.integrator != "rect+cum" or self.n_local % 2:
             raise ValueError("the persistent run streams rect+cum candidates, n_local even")

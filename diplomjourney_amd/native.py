@@ -93,6 +93,14 @@ PROTOTYPES = {
     "mpc_episode_chain_step_obstacles": (c_int, [_CFG, _P, _P, _I32, _I32, c_uint32, _P, _P, _I64,
                                                  _I32, _I64, _I32, _P, _P, c_size_t, _P, _P, _P,
                                                  _P, _I32, _P, _I32, _P, _P]),
+    # ... and keep-out polygons: (polygons, count) after the circles
+    "mpc_episode_partials_keepout": (c_int, [_P, _P, _I32, _P, _I32, _P, _P, _I64, _I32, _I32, _P,
+                                             c_size_t, _P, _P]),
+    "mpc_episode_step_keepout": (c_int, _FINALIZE[:1] + [_P, _I32, _P, _I32] + _FINALIZE[1:-1]
+                                 + [_P, _P]),
+    "mpc_episode_chain_step_keepout": (c_int, [_CFG, _P, _P, _I32, _P, _I32, _I32, c_uint32, _P, _P,
+                                               _I64, _I32, _I64, _I32, _P, _P, c_size_t, _P, _P,
+                                               _P, _P, _I32, _P, _I32, _P, _P]),
     "mpc_episode_run_workspace_bytes": (c_size_t, [_I64]),
     "mpc_episode_run": (c_int, [_CFG, _P, c_uint32, _PP, _PP, _I32, _I64, _I32, _I64, _I32, _P,
                                 c_size_t, _P, _P, _I32, _P]),

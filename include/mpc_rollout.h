@@ -258,8 +258,9 @@ int mpc_rollout_argmin_obstacles(const mpc_problem_t* p, const mpc_obstacle_t* o
  * edge's line (so a zero or non-finite area, a repeated vertex, a collinear
  * triple, a reflex vertex, a bow-tie and a pentagram are all refused).  With
  * valid tables every other rejection is the circle entry's.
- * Polygons are taken by these two entries only: the device-resident episode
- * steps (chained, generated, persistent, exchange and P2P steps included), the
+ * Polygons are taken by these two entries and by the device-resident episode
+ * through mpc_episode_partials_keepout, _step_keepout and _chain_step_keepout
+ * (below, where the episode steps that still take none are listed); the
  * batched one-shot entry, the batched robots, the fleet and the full tree take
  * none; neither are non-convex polygons as one object, swept (between-step)
  * collision, soft penalties, or more than MPC_MAX_POLYGONS polygons of
@@ -511,11 +512,12 @@ int mpc_episode_chain_step(const mpc_episode_config_t* cfg, void* state, int32_t
  * is the base entry's.  n_obstacles == 0 calls the base entry: the same
  * kernels, the same bytes.  EpisodeState and the block records are unchanged,
  * so finalize, the update and the multi-GPU expand / advance step follow as
- * they are.  Without obstacles: the fused step (mpc_episode_rollout), the
- * generated step, the persistent run, the exchange and P2P chained steps and
- * the batched one-shot entry (mpc_rollout_argmin_batched).  (The batched
- * robots' episodes take circles through mpc_episodes_run_obstacles, the full
- * tree and its episodes through the mpc_fulltree_*_obstacles entries.) */
+ * they are.  Without obstacles, circles and polygons alike: the fused step
+ * (mpc_episode_rollout), the generated step, the persistent run, the exchange
+ * and P2P chained steps and the batched one-shot entry
+ * (mpc_rollout_argmin_batched).  (The batched robots' episodes take circles
+ * through mpc_episodes_run_obstacles, the full tree and its episodes through
+ * the mpc_fulltree_*_obstacles entries; none of them takes polygons.) */
 int mpc_episode_partials_obstacles(void* state, const mpc_obstacle_t* obstacles,
                                    int32_t n_obstacles, const double* v_sc,
                                    const double* beta_sc, int64_t n_cand, int32_t n_steps,
@@ -535,6 +537,50 @@ int mpc_episode_chain_step_obstacles(
     const void* ws_prev, size_t ws_bytes, const double* v_prev, const double* beta_prev,
     mpc_result_t* out_prev, const mpc_result_t* gathered, int32_t n_gathered,
     mpc_episode_log_t* log, int32_t log_capacity, int64_t* n_blocked_out, mpc_stream_t stream);
+
+/* Keep-out polygons in the same three steps: the semantics of
+ * mpc_rollout_partials_keepout (strictly inside any polygon or circle blocks a
+ * candidate; step-end states are tested, the start pose is not; a NaN state is
+ * inside nothing; a candidate blocked by a circle and a polygon counts once)
+ * and of the circle entries above (all blocked: `found == 0` / MPC_EP_STALE;
+ * n_blocked_out zeroed on `stream` after every check).  Each entry takes its
+ * _obstacles twin's arguments, plus `polygons, n_polygons` directly after
+ * n_obstacles (a host array, read during the call only: the edge tables travel
+ * as kernel arguments, so a captured graph keeps them).
+ *   mpc_episode_partials_keepout    all five modes, aligned and scalar path
+ *   mpc_episode_step_keepout        that + the unchanged mpc_episode_finalize
+ *   mpc_episode_chain_step_keepout  one GPU, rect + cumulative heading, SoA and
+ *       tiled controls; the tile blocks wait for the published pose before
+ *       their rollout, as with circles (the same bounded wait and chain error)
+ * In MPC_HEADING_CUMULATIVE mode each edge line is moved into the frame of the
+ * step's start pose on the device, from the pose in the episode state, by the
+ * rule the one-shot entry applies on the host (the error bound is that entry's).
+ * MPC_ERR_ARG before any HIP call: first the circles' conditions, then the
+ * polygons' (as mpc_rollout_partials_keepout), then the base entry's in their
+ * stage order.  n_polygons == 0 calls the _obstacles entry (which with no
+ * circles calls the plain one): the same kernels, the same bytes.
+ * EpisodeState, the workspace and the block records are unchanged.  Without
+ * polygons: every step listed above as taking no obstacles. */
+int mpc_episode_partials_keepout(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                                 const mpc_polygon_t* polygons, int32_t n_polygons,
+                                 const double* v_sc, const double* beta_sc, int64_t n_cand,
+                                 int32_t n_steps, int32_t integrator, void* ws, size_t ws_bytes,
+                                 int64_t* n_blocked_out, mpc_stream_t stream);
+int mpc_episode_step_keepout(void* state, const mpc_obstacle_t* obstacles, int32_t n_obstacles,
+                             const mpc_polygon_t* polygons, int32_t n_polygons, const double* v_sc,
+                             const double* beta_sc, int64_t n_cand, int32_t n_steps,
+                             int64_t index_base, int32_t integrator, void* ws, size_t ws_bytes,
+                             mpc_result_t* out, const mpc_episode_config_t* advance,
+                             mpc_episode_log_t* log, int32_t log_capacity, int64_t* n_blocked_out,
+                             mpc_stream_t stream);
+int mpc_episode_chain_step_keepout(
+    const mpc_episode_config_t* cfg, void* state, const mpc_obstacle_t* obstacles,
+    int32_t n_obstacles, const mpc_polygon_t* polygons, int32_t n_polygons, int32_t mode,
+    uint32_t epoch, const double* v_sc, const double* beta_sc, int64_t n_cand, int32_t n_steps,
+    int64_t index_base, int32_t integrator, void* ws, const void* ws_prev, size_t ws_bytes,
+    const double* v_prev, const double* beta_prev, mpc_result_t* out_prev,
+    const mpc_result_t* gathered, int32_t n_gathered, mpc_episode_log_t* log,
+    int32_t log_capacity, int64_t* n_blocked_out, mpc_stream_t stream);
 
 /* Persistent run (one GPU, integrator MPC_INTEG_RECT | MPC_HEADING_CUMULATIVE,
  * SoA or MPC_LAYOUT_TILED controls under the chained step's rules): n_run
